@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - overlaps/s through filter + hinge-detect on the E. coli 160x restatement.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--parts R] [--no-e2e] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--parts R] [--dump-outputs DIR] [--full [--no-e2e] [--no-cpu-baseline]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one whole pass of the `hinge filter` hot path over one batch = R (default 4) DISTINCT E. coli 160x read sets
@@ -14,12 +14,15 @@ exactly as it does in production.  With N > 1 every rank owns one DAZZ_DB block 
 share a 2-block data set, so half of every pile-up's B reads live on the team mate: hinge_amd/benchsets.py) and the path's
 exchange steps run as RCCL collectives between the kernels, batched over the parts: ONE all-reduce (coverage histograms) and
 ONE all-gather (masks) per step (hinge_amd/dist.py, PartBatch).  At every N the hinges of every part of every rank - count and
-a digest of the (read, position, type) rows - are asserted against the CPU oracle's (tests/golden/bench_expect.json).
+a digest of the (read, position, type) rows - are asserted against the CPU oracle's (tests/golden/bench_expect.json) with --full.
 
-At N = 1 rank 0 also reports
+A plain run sets up, warms up, times the K steps and prints the headline line; --dump-outputs DIR also writes what the last timed
+step computed (dump_outputs()).  --full adds, as before: an untimed breakdown pass with events around every kernel and HIP events
+around the dominant kernel in the timed region ("roofline"), the result checks above ("checks") and, at N = 1, on rank 0
   * "e2e": `hinge filter / maximal / layout` (the C++ executables over libhinge_hip, .las ingest and text output included) on the
     part-0 data set written to disk, next to the single-thread CPU oracle on the same files, every output compared byte for byte;
-  * "cpu_baseline": the oracle's filter stage of that same run (the full configuration, not a sample).
+  * "cpu_baseline": the oracle's filter stage of that same run (the full configuration, not a sample);
+  * "consensus", "draft", "maximal_kernel": tools/cns_bench.py, tools/draft_bench.py, tools/k4_bench.py in processes of their own.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).
 """
@@ -33,6 +36,7 @@ import subprocess
 import sys
 import tempfile
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -62,9 +66,62 @@ def parse_args():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="N > 1: weak = every GPU keeps one config-2-sized block per part (teams of two, the default the driver's scaling run "
                          "measures); strong = ONE config-2 data set per part split into N DB blocks (3.3 M overlaps per GPU and part at N = 8)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel breakdown and roofline, the checks against the CPU oracle's expectations and, at N = 1, the e2e, "
+                         "CPU baseline, consensus, draft and maximal-kernel blocks")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) no CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="(--full) none of the N = 1 blocks run in other processes or on disk")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs())")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_BUDGET_BYTES = 60 * 2 ** 20      # under the 64 MB the dump may take
+
+
+def dump_outputs(out_dir, batch, ctxs):
+    """What a caller of the timed path receives after its last step, as float64 (float32 for the coverage bins), to compare two
+    builds output for output (the inputs are seeded: the same arguments give the same read sets).  Per part p:
+      hinges_p<p>    (read, pos, type) rows of the hinges, every rank's (exchange 3), sorted: their order is not part of the result;
+                     reads counted from the first id of the part's table (at N = 1: the read's index in the part)
+      mask_p<p>      [reads, 2] coverage mask, cmask_p<p> [reads, 2] and flags_p<p> [reads] of this rank's block
+      coverage_p<p>  the `.coverage.txt` bins of the block's reads back to back
+      min_cov        [R] MIN_COV every part ended with
+    An array over its share of the budget (60 MiB, what the smaller arrays leave split evenly) is replaced by a fixed, seeded
+    sample of its rows in ascending order, the row indices in `<name>_rows.npy` (they depend only on the array's length).
+    A collective call on every rank; rank 0 writes."""
+    lists = [t.cpu().numpy() for t in batch.hinge_lists()]
+    if batch.rank != 0:
+        return
+    arrays = {}
+    for p, ctx in enumerate(ctxs):
+        rows = lists[p].astype(np.float64)
+        rows[:, 0] -= batch.id_base(p, 0)
+        arrays["hinges_p%d" % p] = rows[np.lexsort(rows.T[::-1])] if len(rows) else rows.reshape(0, 3)
+        mask, cmask, flags = ctx.get_masks()
+        arrays["mask_p%d" % p] = mask.astype(np.float64)
+        arrays["cmask_p%d" % p] = cmask.astype(np.float64)
+        arrays["flags_p%d" % p] = flags.astype(np.float64)
+        arrays["coverage_p%d" % p] = ctx.get_coverage()[1].astype(np.float32)
+    arrays["min_cov"] = np.array([ctx.get_min_cov() for ctx in ctxs], np.float64)
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    large = [a.nbytes > share for a in arrays.values()]
+    if any(large):      # what the arrays under an even share leave goes to the others
+        share = (DUMP_BUDGET_BYTES - sum(a.nbytes for a, l in zip(arrays.values(), large) if not l)) // sum(large)
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for k, (name, a) in enumerate(sorted(arrays.items())):
+        row_bytes = a.itemsize * int(np.prod(a.shape[1:], dtype=np.int64))
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(1000 + k).choice(len(a), size=share // (row_bytes + 8), replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), keep.astype(np.float64))
+            total += keep.nbytes
+            a = a[keep]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        total += a.nbytes
+    assert total <= 64 * 10 ** 6, total
 
 
 def pmc_traffic(kname, batched=False):
@@ -309,16 +366,20 @@ def main():
     P = default_filter_params()
     R = max(1, args.parts)
     base = synth.CONFIGS[args.workload]
-    t_gen = time.perf_counter()
-    first_data = None
-    parts = []
-    for p in range(R):
+    keep_first = world == 1 and args.full and not args.no_e2e      # end_to_end() writes part 0's data set to disk
+
+    def make_part(p):
         spec, _ = benchsets.part_spec(base, world, rank, p, args.scaling)
-        d = synth.generate(spec)
-        if p == 0 and world == 1:
-            first_data = d
-        parts.append(benchsets.rank_part(base, world, rank, p, data=d, scaling=args.scaling))
-        del d
+        d = synth.generate(spec)          # (its own seeded generator: the same read sets in any thread)
+        return benchsets.rank_part(base, world, rank, p, data=d, scaling=args.scaling), (d if p == 0 and keep_first else None)
+
+    # the parts are independent and the generator is numpy throughout (it releases the GIL): one thread per part, at most 4
+    t_gen = time.perf_counter()
+    with ThreadPoolExecutor(max_workers=min(R, 4)) as pool:
+        made = list(pool.map(make_part, range(R)))
+    parts = [rp for rp, _ in made]
+    first_data = made[0][1]
+    del made
     t_gen = time.perf_counter() - t_gen
     # every block gets the same number of read ids (the largest block's over all ranks and parts; the ids behind a block's
     # reads are reads of length 0 without overlaps), so the mask tables are exchanged by in-place all-gathers
@@ -356,28 +417,29 @@ def main():
         one_step()
     batch.status()
 
-    # ---- untimed breakdown pass: events around EVERY kernel (they cost stream time, so the timed region below brackets
-    # only the kernel it prices) --------------------------------------------------------------------------------------
-    n_break = max(2, min(args.steps, 5))
-    for ctx in ctxs:
-        ctx.profile_select(None)
-        ctx.profile_enable(12 * n_break + 16)
-    for _ in range(n_break):
-        one_step()
-    sync()
-    breakdown = {}
-    for ctx in ctxs:
-        ctx.check()
-        for k, (ms, cnt) in ctx.profile_report().items():
-            a = breakdown.setdefault(k, [0.0, 0])
-            a[0] += ms; a[1] += cnt
-        ctx.profile_enable(0)
-    dominant = max(((k, v) for k, v in breakdown.items() if v[1] > 0), key=lambda kv: kv[1][0])[0]
+    # ---- --full: an untimed breakdown pass, events around EVERY kernel (they cost stream time, so the timed region below
+    # brackets only the kernel it prices) -------------------------------------------------------------------------------
+    if args.full:
+        n_break = max(2, min(args.steps, 5))
+        for ctx in ctxs:
+            ctx.profile_select(None)
+            ctx.profile_enable(12 * n_break + 16)
+        for _ in range(n_break):
+            one_step()
+        sync()
+        breakdown = {}
+        for ctx in ctxs:
+            ctx.check()
+            for k, (ms, cnt) in ctx.profile_report().items():
+                a = breakdown.setdefault(k, [0.0, 0])
+                a[0] += ms; a[1] += cnt
+            ctx.profile_enable(0)
+        dominant = max(((k, v) for k, v in breakdown.items() if v[1] > 0), key=lambda kv: kv[1][0])[0]
+        for ctx in ctxs:
+            ctx.profile_select([dominant])
+            ctx.profile_enable(2 * args.steps + 16)
 
-    # ---- timed region: K steps, HIP events around the dominant kernel only ---------------------------------
-    for ctx in ctxs:
-        ctx.profile_select([dominant])
-        ctx.profile_enable(2 * args.steps + 16)
+    # ---- timed region: K steps (--full: HIP events around the dominant kernel only) ---------------------------------
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -385,34 +447,39 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     batch.status()
-    prof_ms, prof_cnt = 0.0, 0
-    for ctx in ctxs:
-        ms, cnt = ctx.profile_report()[dominant]
-        prof_ms += ms; prof_cnt += cnt
-        ctx.profile_enable(0)
-        ctx.profile_select(None)
+    if args.full:
+        prof_ms, prof_cnt = 0.0, 0
+        for ctx in ctxs:
+            ms, cnt = ctx.profile_report()[dominant]
+            prof_ms += ms; prof_cnt += cnt
+            ctx.profile_enable(0)
+            ctx.profile_select(None)
 
-    # ---- results, outside the timed region: exchange 3 (the (read, pos, type) rows of every part from every rank, on every
-    # rank) and the per-rank counters --------------------------------------------------------------------------------
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, batch, ctxs)
+
+    # ---- results, outside the timed region: the per-rank counters and, with --full, exchange 3 (the (read, pos, type) rows
+    # of every part from every rank, on every rank) ------------------------------------------------------------------
     spec_stats = [[int(v) for v in ctx.spec_stats()] for ctx in ctxs]   # one-sweep pass: verifications, mispredictions, guard-band reads
-    lists = [t.cpu().numpy() for t in batch.hinge_lists()]
     work_reads = sum(int(ctx.counters()[0]) for ctx in ctxs)
     exact_annos = sum(int(ctx.counters()[1]) for ctx in ctxs)
-    table_sums = batch.table_checksums()                    # every rank must hold the same mask tables after exchange 2
-    all_sums = host_all_gather(table_sums)
-    got = []                                                # [part][rank] -> {"hinges", "digest"}
-    for p in range(R):
-        rows = lists[p]
-        per_rank = []
-        for r in range(world):
-            lo = batch.id_base(p, r)
-            sel = (rows[:, 0] >= lo) & (rows[:, 0] < lo + S)
-            loc = rows[sel].astype(np.int64)
-            loc[:, 0] -= lo
-            per_rank.append({"hinges": int(len(loc)), "digest": benchsets.digest(loc)})
-        assert sum(e["hinges"] for e in per_rank) == len(rows)
-        got.append(per_rank)
-    sizes = host_all_gather(part_reads + part_records)      # [rank] -> reads of every part, then records of every part
+    if args.full:
+        lists = [t.cpu().numpy() for t in batch.hinge_lists()]
+        table_sums = batch.table_checksums()                    # every rank must hold the same mask tables after exchange 2
+        all_sums = host_all_gather(table_sums)
+        got = []                                                # [part][rank] -> {"hinges", "digest"}
+        for p in range(R):
+            rows = lists[p]
+            per_rank = []
+            for r in range(world):
+                lo = batch.id_base(p, r)
+                sel = (rows[:, 0] >= lo) & (rows[:, 0] < lo + S)
+                loc = rows[sel].astype(np.int64)
+                loc[:, 0] -= lo
+                per_rank.append({"hinges": int(len(loc)), "digest": benchsets.digest(loc)})
+            assert sum(e["hinges"] for e in per_rank) == len(rows)
+            got.append(per_rank)
+        sizes = host_all_gather(part_reads + part_records)      # [rank] -> reads of every part, then records of every part
 
     if use_pg:
         d_ = dev if pg_backend == "nccl" else torch.device("cpu")
@@ -428,138 +495,139 @@ def main():
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
         value = total_ovl * args.steps / elapsed
-        kname = dominant
-        avg_ms = prof_ms / max(prof_cnt, 1)              # mean launch time over the timed region's launches
-        # parts per launch: 1 when every part has a launch of its own, R when one launch sweeps all resident parts (the batched
-        # k_mask_annotate_q20) - from the launch count itself, so reruns of a part count as launches
-        ppl = R * args.steps / max(prof_cnt, 1)
         n_reads = sum(part_reads)
-        if kname not in KERNEL_BYTES_PER_OVERLAP:
-            alg_bytes = achieved = phys_bytes = None      # sparse kernel: touches only the work-list reads
-        else:
-            alg_bytes = (KERNEL_BYTES_PER_OVERLAP[kname] * n_ovl + KERNEL_BYTES_PER_READ[kname] * n_reads) / R * ppl   # mean per launch
-            achieved = alg_bytes / (avg_ms * 1e-3) / 1e9
-            # what the kernel has to move: the 16|16 span copy (4 B per overlap, packed by the ingest), the per-read tables and,
-            # for the mask / annotate kernel, the coverage bins it stores
-            phys_bytes = (4 * n_ovl + KERNEL_BYTES_PER_READ[kname] * n_reads + (4 * sum(part_bins) if kname == "k_mask_annotate" else 0)) / R * ppl
-        one_sweep = bool(getattr(batch, "one_sweep", False)) and "k_cov_stats" not in {k for k, v in breakdown.items() if v[1] > 0}
-        traffic, traffic_src = pmc_traffic(kname, batched=ppl > 1.5)
-        resident = sum(part_ovl) * (8 + 8 + 4 + 4) + sum(part_bins) * 4
-        roofline = {
-            "bound": "hbm",
-            "kernel": kname,
-            "achieved": achieved,
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": (achieved / HBM_PEAK_GBS) if achieved is not None else None,
-            "traffic": traffic,
-            "traffic_source": traffic_src,
-            "avg_launch_ms": avg_ms,
-            "launches_timed": prof_cnt,
-            "parts_per_launch": ppl,
-            "algorithmic_bytes_per_launch": alg_bytes,
-            "physical_bytes_per_launch": phys_bytes,
-            "achieved_physical": (phys_bytes / (avg_ms * 1e-3) / 1e9) if phys_bytes else None,
-            "frac_physical": (phys_bytes / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if phys_bytes else None,
-            "waste_ratio": (traffic / phys_bytes) if (traffic and phys_bytes) else None,
-            "one_sweep_note": ("the dominant kernel is the FIRST AND ONLY sweep of the pass (DESIGN.md 3.6): it does the work SURVEY 8(d) prices as pass 1 (8 B per overlap) "
-                               "plus pass 2's span read (8 B per overlap); `frac` keeps crediting it 8 B per overlap - what one sweep has to read - so it is "
-                               "comparable with rounds 1-3, where a second kernel (k_cov_stats, 32 us per part) was credited the other 8") if one_sweep else None,
-            "frac_if_credited_both_passes": ((alg_bytes + (8 * n_ovl / R + 20 * n_reads / R) * ppl) / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (one_sweep and achieved is not None and kname == "k_mask_annotate") else None,
-            "physical_note": "`frac` credits SURVEY 8(d)'s 8 B per overlap (the int32 span pair); the kernel reads the ingest's 16|16 copy (4 B per "
-                             "overlap) and, unlike 8(d)'s accounting, writes the coverage bins: physical = 4 B x overlaps + per-read tables + bins; "
-                             "waste_ratio = counter traffic / physical",
-            "coverage_bins_bytes_per_launch": 4 * sum(part_bins) / R * ppl if kname == "k_mask_annotate" else None,
-            "coverage_bins_note": "k_mask_annotate also stores the cutoff-0 coverage bins (.coverage.txt payload, ~4 B x (rlen/40 + 2) per read); "
-                                  "they are NOT counted in `achieved`",
-            "kernels_ms_per_step": {k: v[0] / n_break for k, v in breakdown.items() if v[1] > 0},
-            "kernels_ms_note": "untimed breakdown pass with events around every kernel (includes event overhead), summed over the %d parts of a step; "
-                               "avg_launch_ms is from the timed region" % R,
-            "working_set": "%d distinct resident parts, %.2f GB of pile-up columns + span copies + bin output in total; a pass's sweep(s) "
-                           "read %.0f MB (16|16 span copy) per part and K2 writes %.0f MB of bins; %.2f GB pass through between two visits of the same part "
-                           "(Infinity Cache: 256 MiB)" % (R, resident / 1e9, 4 * n_ovl / R / 1e6, 4 * sum(part_bins) / R / 1e6, (R - 1) * (4 * n_ovl / R + 4 * sum(part_bins) / R) / 1e9),
-            "path_bytes_per_overlap": PATH_BYTES_PER_OVERLAP,
-            "path_credit_GBs": PATH_BYTES_PER_OVERLAP * n_ovl / (ms_per_step * 1e-3) / 1e9,
-            "path_credit_note": "SURVEY 8(d)'s 40 B per overlap x overlaps / step time: a figure of merit for the whole path, NOT achieved bandwidth "
-                                "(the design reads ~16 B per overlap)",
-        }
-        # ---- results are checked, not just printed: at EVERY N, every part of every rank against the CPU oracle's hinge count
-        # and row digest (tests/golden/bench_expect.json, tools/make_bench_expect.py) ----------------------------------
-        expect_path = os.environ.get("HINGE_BENCH_EXPECT") or os.path.join(ROOT, "tests", "golden", "bench_expect.json")
-        expect = json.load(open(expect_path)).get(args.workload, {}).get("worlds", {}).get("1" if strong else str(world), {}) if os.path.exists(expect_path) else {}
-        if strong:
-            # strong scaling: the N blocks are ONE config-2 data set, merged-las semantics - the union of the ranks' rows, in
-            # the data set's own read ids, must be the N = 1 result (the committed expectation of world 1)
-            merged = []
+        if args.full:
+            kname = dominant
+            avg_ms = prof_ms / max(prof_cnt, 1)              # mean launch time over the timed region's launches
+            # parts per launch: 1 when every part has a launch of its own, R when one launch sweeps all resident parts (the batched
+            # k_mask_annotate_q20) - from the launch count itself, so reruns of a part count as launches
+            ppl = R * args.steps / max(prof_cnt, 1)
+            if kname not in KERNEL_BYTES_PER_OVERLAP:
+                alg_bytes = achieved = phys_bytes = None      # sparse kernel: touches only the work-list reads
+            else:
+                alg_bytes = (KERNEL_BYTES_PER_OVERLAP[kname] * n_ovl + KERNEL_BYTES_PER_READ[kname] * n_reads) / R * ppl   # mean per launch
+                achieved = alg_bytes / (avg_ms * 1e-3) / 1e9
+                # what the kernel has to move: the 16|16 span copy (4 B per overlap, packed by the ingest), the per-read tables and,
+                # for the mask / annotate kernel, the coverage bins it stores
+                phys_bytes = (4 * n_ovl + KERNEL_BYTES_PER_READ[kname] * n_reads + (4 * sum(part_bins) if kname == "k_mask_annotate" else 0)) / R * ppl
+            one_sweep = bool(getattr(batch, "one_sweep", False)) and "k_cov_stats" not in {k for k, v in breakdown.items() if v[1] > 0}
+            traffic, traffic_src = pmc_traffic(kname, batched=ppl > 1.5)
+            resident = sum(part_ovl) * (8 + 8 + 4 + 4) + sum(part_bins) * 4
+            roofline = {
+                "bound": "hbm",
+                "kernel": kname,
+                "achieved": achieved,
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "frac": (achieved / HBM_PEAK_GBS) if achieved is not None else None,
+                "traffic": traffic,
+                "traffic_source": traffic_src,
+                "avg_launch_ms": avg_ms,
+                "launches_timed": prof_cnt,
+                "parts_per_launch": ppl,
+                "algorithmic_bytes_per_launch": alg_bytes,
+                "physical_bytes_per_launch": phys_bytes,
+                "achieved_physical": (phys_bytes / (avg_ms * 1e-3) / 1e9) if phys_bytes else None,
+                "frac_physical": (phys_bytes / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if phys_bytes else None,
+                "waste_ratio": (traffic / phys_bytes) if (traffic and phys_bytes) else None,
+                "one_sweep_note": ("the dominant kernel is the FIRST AND ONLY sweep of the pass (DESIGN.md 3.6): it does the work SURVEY 8(d) prices as pass 1 (8 B per overlap) "
+                                   "plus pass 2's span read (8 B per overlap); `frac` keeps crediting it 8 B per overlap - what one sweep has to read - so it is "
+                                   "comparable with rounds 1-3, where a second kernel (k_cov_stats, 32 us per part) was credited the other 8") if one_sweep else None,
+                "frac_if_credited_both_passes": ((alg_bytes + (8 * n_ovl / R + 20 * n_reads / R) * ppl) / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (one_sweep and achieved is not None and kname == "k_mask_annotate") else None,
+                "physical_note": "`frac` credits SURVEY 8(d)'s 8 B per overlap (the int32 span pair); the kernel reads the ingest's 16|16 copy (4 B per "
+                                 "overlap) and, unlike 8(d)'s accounting, writes the coverage bins: physical = 4 B x overlaps + per-read tables + bins; "
+                                 "waste_ratio = counter traffic / physical",
+                "coverage_bins_bytes_per_launch": 4 * sum(part_bins) / R * ppl if kname == "k_mask_annotate" else None,
+                "coverage_bins_note": "k_mask_annotate also stores the cutoff-0 coverage bins (.coverage.txt payload, ~4 B x (rlen/40 + 2) per read); "
+                                      "they are NOT counted in `achieved`",
+                "kernels_ms_per_step": {k: v[0] / n_break for k, v in breakdown.items() if v[1] > 0},
+                "kernels_ms_note": "untimed breakdown pass with events around every kernel (includes event overhead), summed over the %d parts of a step; "
+                                   "avg_launch_ms is from the timed region" % R,
+                "working_set": "%d distinct resident parts, %.2f GB of pile-up columns + span copies + bin output in total; a pass's sweep(s) "
+                               "read %.0f MB (16|16 span copy) per part and K2 writes %.0f MB of bins; %.2f GB pass through between two visits of the same part "
+                               "(Infinity Cache: 256 MiB)" % (R, resident / 1e9, 4 * n_ovl / R / 1e6, 4 * sum(part_bins) / R / 1e6, (R - 1) * (4 * n_ovl / R + 4 * sum(part_bins) / R) / 1e9),
+                "path_bytes_per_overlap": PATH_BYTES_PER_OVERLAP,
+                "path_credit_GBs": PATH_BYTES_PER_OVERLAP * n_ovl / (ms_per_step * 1e-3) / 1e9,
+                "path_credit_note": "SURVEY 8(d)'s 40 B per overlap x overlaps / step time: a figure of merit for the whole path, NOT achieved bandwidth "
+                                    "(the design reads ~16 B per overlap)",
+            }
+            # ---- results are checked, not just printed: at EVERY N, every part of every rank against the CPU oracle's hinge count
+            # and row digest (tests/golden/bench_expect.json, tools/make_bench_expect.py) ----------------------------------
+            expect_path = os.environ.get("HINGE_BENCH_EXPECT") or os.path.join(ROOT, "tests", "golden", "bench_expect.json")
+            expect = json.load(open(expect_path)).get(args.workload, {}).get("worlds", {}).get("1" if strong else str(world), {}) if os.path.exists(expect_path) else {}
+            if strong:
+                # strong scaling: the N blocks are ONE config-2 data set, merged-las semantics - the union of the ranks' rows, in
+                # the data set's own read ids, must be the N = 1 result (the committed expectation of world 1)
+                merged = []
+                for p in range(R):
+                    first = np.concatenate([[0], np.cumsum([sizes[r][p] for r in range(world)])])
+                    rows = lists[p].astype(np.int64)
+                    out_rows = []
+                    for r in range(world):
+                        lo = batch.id_base(p, r)
+                        sel = (rows[:, 0] >= lo) & (rows[:, 0] < lo + S)
+                        loc = rows[sel].copy()
+                        loc[:, 0] += int(first[r]) - lo
+                        out_rows.append(loc)
+                    allr = np.concatenate(out_rows) if out_rows else np.zeros((0, 3), np.int64)
+                    merged.append([{"hinges": int(len(allr)), "digest": benchsets.digest(allr)}])
+                per_rank_got, got = got, merged
+                sizes = [[sum(sizes[r][p] for r in range(world)) for p in range(2 * R)]]
+            checks = {"hinges_per_part_and_rank": [[e["hinges"] for e in pr] for pr in (per_rank_got if strong else got)], "parts_checked": 0,
+                      "mask_tables_identical_on_all_ranks": all(s_ == all_sums[0] for s_ in all_sums)}
+            assert checks["mask_tables_identical_on_all_ranks"], "exchange 2 left different mask tables on different ranks: %s" % (all_sums,)
             for p in range(R):
-                first = np.concatenate([[0], np.cumsum([sizes[r][p] for r in range(world)])])
-                rows = lists[p].astype(np.int64)
-                out_rows = []
-                for r in range(world):
-                    lo = batch.id_base(p, r)
-                    sel = (rows[:, 0] >= lo) & (rows[:, 0] < lo + S)
-                    loc = rows[sel].copy()
-                    loc[:, 0] += int(first[r]) - lo
-                    out_rows.append(loc)
-                allr = np.concatenate(out_rows) if out_rows else np.zeros((0, 3), np.int64)
-                merged.append([{"hinges": int(len(allr)), "digest": benchsets.digest(allr)}])
-            per_rank_got, got = got, merged
-            sizes = [[sum(sizes[r][p] for r in range(world)) for p in range(2 * R)]]
-        checks = {"hinges_per_part_and_rank": [[e["hinges"] for e in pr] for pr in (per_rank_got if strong else got)], "parts_checked": 0,
-                  "mask_tables_identical_on_all_ranks": all(s_ == all_sums[0] for s_ in all_sums)}
-        assert checks["mask_tables_identical_on_all_ranks"], "exchange 2 left different mask tables on different ranks: %s" % (all_sums,)
-        for p in range(R):
-            want = expect.get(str(p))
-            if want is None or os.environ.get("HINGE_BENCH_NO_ASSERT") == "1":     # (NO_ASSERT: ablation builds produce garbage on purpose)
-                continue
-            have_sizes = ([sizes[r][p] for r in range(len(sizes))], [sizes[r][R + p] for r in range(len(sizes))])
-            assert (want["reads"], want["records"]) == have_sizes, "part %d: the generated read sets %s are not the ones the expectations were made for %s" % (p, have_sizes, (want["reads"], want["records"]))
-            assert want["ranks"] == got[p], "part %d: hinges (count, digest) per rank %s differ from the CPU oracle's %s" % (p, got[p], want["ranks"])
-            checks["parts_checked"] += 1
-        checks["hinges_and_digests_match_cpu_oracle"] = checks["parts_checked"] > 0
-        assert checks["parts_checked"] > 0 or R > 4 or args.workload != "cfg2_ecoli160" or os.environ.get("HINGE_BENCH_NO_ASSERT") == "1", "no committed expectation for N = %d" % world
-        e2e = cpu = None
-        if world == 1 and not args.no_e2e:
-            e2e, cpu, oracle_hinges = end_to_end(first_data, args.workload)
-            checks["hinges_part0_vs_live_oracle_run"] = [got[0][0]["hinges"], oracle_hinges]
-            assert got[0][0]["hinges"] == oracle_hinges, "resident pass found %d hinges on part 0, the oracle's .hinges.txt has %d" % (got[0][0]["hinges"], oracle_hinges)
-            assert e2e["byte_identical"], "executables differ from the oracle: %s" % e2e["files_differing"]
-            if args.no_cpu_baseline:
-                cpu = None
-        consensus = None
-        if world == 1 and not args.no_e2e:
-            # SURVEY 8(f-4), reported beside the headline metric: `hinge consensus` at E. coli size (tools/cns_bench.py) - the
-            # reference's own program (oracle/_ref/consensus, where it was built) against the executable and the kernels; FASTA
-            # byte-identical or the run fails
-            try:
-                r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "cns_bench.py")] + (["--no-cpu"] if args.no_cpu_baseline else []),
-                                   stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
-                assert r.returncode == 0, r.stderr.decode()[-1500:]
-                consensus = json.loads(r.stdout.decode().strip().splitlines()[-1])
-            except Exception as ex:      # (reported, not fatal: the headline metric is the filter path's)
-                consensus = {"error": str(ex)[-800:]}
-        draft = None
-        if world == 1 and not args.no_e2e:
-            # SURVEY 8(f-4), `hinge draft`'s ladder step at E. coli size (tools/draft_bench.py): k_draft_align + k_draft_cns on 5 000
-            # ladders of ~25 members against the reference's OWN falcon (oracle/_ref: falcon.c + DW_banded.c unmodified) on a sample
-            # of the same ladders, byte-identical or the run fails
-            try:
-                r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "draft_bench.py")] + (["--no-cpu"] if args.no_cpu_baseline else []),
-                                   stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
-                assert r.returncode == 0, r.stderr.decode()[-1500:]
-                draft = json.loads(r.stdout.decode().strip().splitlines()[-1])
-            except Exception as ex:      # (reported, not fatal)
-                draft = {"error": str(ex)[-800:]}
-        maximal_kernel = None
-        if world == 1 and not args.no_e2e:
-            # SURVEY 8(a) rows 14-15, reported beside the headline metric: the kernel `hinge maximal` runs over every overlap of the
-            # bench part (tools/k4_bench.py --json: k_trim_classify_image, launch time from HIP events, its own roofline)
-            try:
-                r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "k4_bench.py"), "--json", "--reps", "5"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
-                assert r.returncode == 0, r.stderr.decode()[-1500:]
-                maximal_kernel = json.loads(r.stdout.decode().strip().splitlines()[-1])
-            except Exception as ex:      # (reported, not fatal)
-                maximal_kernel = {"error": str(ex)[-800:]}
+                want = expect.get(str(p))
+                if want is None or os.environ.get("HINGE_BENCH_NO_ASSERT") == "1":     # (NO_ASSERT: ablation builds produce garbage on purpose)
+                    continue
+                have_sizes = ([sizes[r][p] for r in range(len(sizes))], [sizes[r][R + p] for r in range(len(sizes))])
+                assert (want["reads"], want["records"]) == have_sizes, "part %d: the generated read sets %s are not the ones the expectations were made for %s" % (p, have_sizes, (want["reads"], want["records"]))
+                assert want["ranks"] == got[p], "part %d: hinges (count, digest) per rank %s differ from the CPU oracle's %s" % (p, got[p], want["ranks"])
+                checks["parts_checked"] += 1
+            checks["hinges_and_digests_match_cpu_oracle"] = checks["parts_checked"] > 0
+            assert checks["parts_checked"] > 0 or R > 4 or args.workload != "cfg2_ecoli160" or os.environ.get("HINGE_BENCH_NO_ASSERT") == "1", "no committed expectation for N = %d" % world
+            e2e = cpu = None
+            if world == 1 and not args.no_e2e:
+                e2e, cpu, oracle_hinges = end_to_end(first_data, args.workload)
+                checks["hinges_part0_vs_live_oracle_run"] = [got[0][0]["hinges"], oracle_hinges]
+                assert got[0][0]["hinges"] == oracle_hinges, "resident pass found %d hinges on part 0, the oracle's .hinges.txt has %d" % (got[0][0]["hinges"], oracle_hinges)
+                assert e2e["byte_identical"], "executables differ from the oracle: %s" % e2e["files_differing"]
+                if args.no_cpu_baseline:
+                    cpu = None
+            consensus = None
+            if world == 1 and not args.no_e2e:
+                # SURVEY 8(f-4), reported beside the headline metric: `hinge consensus` at E. coli size (tools/cns_bench.py) - the
+                # reference's own program (oracle/_ref/consensus, where it was built) against the executable and the kernels; FASTA
+                # byte-identical or the run fails
+                try:
+                    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "cns_bench.py")] + (["--no-cpu"] if args.no_cpu_baseline else []),
+                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                    assert r.returncode == 0, r.stderr.decode()[-1500:]
+                    consensus = json.loads(r.stdout.decode().strip().splitlines()[-1])
+                except Exception as ex:      # (reported, not fatal: the headline metric is the filter path's)
+                    consensus = {"error": str(ex)[-800:]}
+            draft = None
+            if world == 1 and not args.no_e2e:
+                # SURVEY 8(f-4), `hinge draft`'s ladder step at E. coli size (tools/draft_bench.py): k_draft_align + k_draft_cns on 5 000
+                # ladders of ~25 members against the reference's OWN falcon (oracle/_ref: falcon.c + DW_banded.c unmodified) on a sample
+                # of the same ladders, byte-identical or the run fails
+                try:
+                    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "draft_bench.py")] + (["--no-cpu"] if args.no_cpu_baseline else []),
+                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                    assert r.returncode == 0, r.stderr.decode()[-1500:]
+                    draft = json.loads(r.stdout.decode().strip().splitlines()[-1])
+                except Exception as ex:      # (reported, not fatal)
+                    draft = {"error": str(ex)[-800:]}
+            maximal_kernel = None
+            if world == 1 and not args.no_e2e:
+                # SURVEY 8(a) rows 14-15, reported beside the headline metric: the kernel `hinge maximal` runs over every overlap of the
+                # bench part (tools/k4_bench.py --json: k_trim_classify_image, launch time from HIP events, its own roofline)
+                try:
+                    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "k4_bench.py"), "--json", "--reps", "5"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                    assert r.returncode == 0, r.stderr.decode()[-1500:]
+                    maximal_kernel = json.loads(r.stdout.decode().strip().splitlines()[-1])
+                except Exception as ex:      # (reported, not fatal)
+                    maximal_kernel = {"error": str(ex)[-800:]}
         collectives = batch.collectives
         out = {
             "metric": "overlaps/sec through filter+hinge-detect, E. coli 160x" if args.workload == "cfg2_ecoli160" else "overlaps/sec through filter+hinge-detect, %s (NOT the headline configuration)" % args.workload,
@@ -594,19 +662,15 @@ def main():
                                    "k_hinge_count, k_hinge_call - every one of them ONE launch for all parts; none outside.  HINGE_K2_BATCH=0: a k_mask_annotate launch per part; HINGE_ONE_SWEEP=0: k_cov_stats first (rounds 1-3)",
                 "one_sweep": {"per_part": [{"passes_verified": s_[0], "exact_differs_from_prediction": s_[1], "prediction_outside_band_whole_part_redone": s_[2],
                                             "guard_band_reads_last_pass": s_[3], "predicted_min_cov": s_[4], "exact_min_cov": s_[5]} for s_ in spec_stats],
-                              "note": "cumulative over warm-up, breakdown and timed steps; redone parts and guard-band launches are inside the timed region"},
+                              "note": "cumulative over warm-up, (--full) breakdown and timed steps; redone parts and guard-band launches are inside the timed region"},
                 "reads_in_hinge_pass": work_reads,
                 "annotations_on_exact_path": exact_annos,
                 "generate_s": t_gen,
             },
-            "roofline": roofline,
-            "checks": checks,
-            "e2e": e2e,
-            "draft": draft,
-            "consensus": consensus,
-            "maximal_kernel": maximal_kernel,
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            out.update({"roofline": roofline, "checks": checks, "e2e": e2e, "draft": draft, "consensus": consensus,
+                        "maximal_kernel": maximal_kernel, "cpu_baseline": cpu})
         print(json.dumps(out))
     if use_pg:
         dist.barrier()

@@ -330,14 +330,14 @@ def test_part_batch_mixed_parts_share_launches(oracle_lib):
     assert used[0][1] > 0, "no annotation of the deep part reached the large instance: %s" % (used,)
 
 
-# ---- bench.py itself with two ranks, and with a deliberately broken exchange 2 ---------------------------------------------
+# ---- bench.py itself: with two ranks, with a deliberately broken exchange 2, and the outputs it dumps -------------------------
 def _run_bench(extra_env, workload="chimera", nproc=2):
     env = dict(os.environ)
     env.update({"HINGE_BENCH_BACKEND": "gloo", "HINGE_BENCH_ONE_DEVICE": "1", "HINGE_BENCH_EXPECT": extra_env.pop("expect")})
     env.update(extra_env)
     port = conftest.free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "3", "--warmup", "1", "--workload", workload, "--parts", "2"]
+           os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "3", "--warmup", "1", "--workload", workload, "--parts", "2", "--full"]
     return subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
 
 
@@ -363,3 +363,26 @@ def test_bench_two_ranks_asserts_results(oracle_lib, tmp_path):
     assert line["config"]["collectives_per_step"] == 2
     bad = _run_bench({"expect": path, "HINGE_TEST_CORRUPT_GATHER": "1"})
     assert bad.returncode != 0 and (b"differ from the CPU oracle" in bad.stderr or b"different mask tables on different ranks" in bad.stderr), bad.stderr.decode()[-2000:]
+
+
+def test_bench_dump_outputs_are_the_oracle_results(oracle_lib, tmp_path):
+    """bench.py --dump-outputs on one rank (a plain run: no checks of its own): every part's dumped hinge rows are the CPU
+    oracle's (count + row digest), MIN_COV and the per-read tables are there, and the dump stays under 64 MB."""
+    import json
+    from hinge_amd import benchsets
+    want = _oracle_expectation(oracle_lib, "chimera", 1, 2)
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "chimera",
+                        "--parts", "2", "--dump-outputs", str(out)], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    line = json.loads(r.stdout.decode().strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and "checks" not in line
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 * 10 ** 6
+    for p in range(2):
+        rows = np.load(out / ("hinges_p%d.npy" % p))
+        assert rows.dtype == np.float64 and rows.shape[1] == 3
+        assert [{"hinges": len(rows), "digest": benchsets.digest(rows.astype(np.int64))}] == want[p], p
+        mask = np.load(out / ("mask_p%d.npy" % p))
+        assert mask.shape == np.load(out / ("cmask_p%d.npy" % p)).shape and mask.shape[0] == len(np.load(out / ("flags_p%d.npy" % p)))
+        assert np.load(out / ("coverage_p%d.npy" % p)).dtype == np.float32
+    assert np.load(out / "min_cov.npy").shape == (2,)

@@ -34,14 +34,14 @@ python -m pytest tests/test_zz_comm_multi_gpu.py -x -q -m gpu > "$OUT/1_comm.log
 PORT=29610
 n=1
 while [ "$n" -le "$N" ]; do
-  if [ "$n" -eq 1 ]; then python bench.py --gpus 1 --no-e2e > "$OUT/2_bench_n1.json" 2> "$OUT/2_bench_n1.err"
-  else python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus "$n" --no-e2e > "$OUT/2_bench_n$n.json" 2> "$OUT/2_bench_n$n.err"; fi
+  if [ "$n" -eq 1 ]; then python bench.py --gpus 1 --full --no-e2e > "$OUT/2_bench_n1.json" 2> "$OUT/2_bench_n1.err"
+  else python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus "$n" --full --no-e2e > "$OUT/2_bench_n$n.json" 2> "$OUT/2_bench_n$n.err"; fi
   rc=$?; tail -1 "$OUT/2_bench_n$n.json" >> "$OUT/scale.jsonl"
   note "2 bench weak n=$n: rc=$rc $(tail -1 "$OUT/2_bench_n$n.json" | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print("value=%.4g ms_per_step=%.4f checks=%s" % (d["value"], d["ms_per_step"], d["checks"]["hinges_and_digests_match_cpu_oracle"]))' 2>/dev/null)"
   PORT=$((PORT + 1)); n=$((n * 2))
 done
-if [ "$N" -ge 2 ]; then python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus "$N" --scaling strong --no-e2e > "$OUT/3_bench_strong_n$N.json" 2> "$OUT/3_bench_strong_n$N.err"
-else python bench.py --gpus 1 --scaling strong --no-e2e > "$OUT/3_bench_strong_n$N.json" 2> "$OUT/3_bench_strong_n$N.err"; fi
+if [ "$N" -ge 2 ]; then python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus "$N" --scaling strong --full --no-e2e > "$OUT/3_bench_strong_n$N.json" 2> "$OUT/3_bench_strong_n$N.err"
+else python bench.py --gpus 1 --scaling strong --full --no-e2e > "$OUT/3_bench_strong_n$N.json" 2> "$OUT/3_bench_strong_n$N.err"; fi
 rc=$?; tail -1 "$OUT/3_bench_strong_n$N.json" >> "$OUT/scale.jsonl"; note "3 bench strong n=$N: rc=$rc"
 
 if [ "$N" -ge 2 ]; then python tools/mlas_rccl_check.py > "$OUT/4_mlas_rccl.log" 2>&1; else python tools/mlas_rccl_check.py --one-rank > "$OUT/4_mlas_rccl.log" 2>&1; fi
