@@ -602,7 +602,13 @@ class Draft:
         return [out[off[i]:off[i + 1]] for i in range(len(picks))]
 
     def ladders(self, ladders, templates, band: int = 150):
-        """ladders: list of lists of (read, strand, start, end); templates: the template member of each.  Returns the consensus strings."""
+        """ladders: list of lists of (read, strand, start, end); templates: the template member of each.  Returns the consensus strings.
+
+        A ladder has 1 .. 65535 members (the reference's vote counters are 16-bit) of any length, its template fewer than 2^21
+        bases (a tag's position field); ladders of 65+ members and members of 32768+ bases (or member + template beyond the
+        aligner's LDS) take the deep / long kernels, byte-identical to the reference's falcon like the rest.  HingeError:
+        HINGE_E_CAPACITY beyond those bounds, HINGE_E_RANGE for 255+ inserted bases in a row and HINGE_E_UNDEFINED for a ladder
+        without a scoring column (both undefined in the reference) - each fails the whole call."""
         n = len(ladders)
         rung_off = np.concatenate([[0], np.cumsum([len(x) for x in ladders])]).astype(np.int64)
         rungs = np.zeros(max(int(rung_off[-1]), 1), dtype=self.RUNG_DTYPE)

@@ -15,6 +15,8 @@
 //                   the reference's insertion order, so ties fall the same way), scores as doubled integers (the reference adds
 //                   link counts and halves of the coverage: exact in either form), the best-predecessor table in HBM, the
 //                   trace-back by lane 0 - including the reference's habit of deciding the LAST base by a link index
+//   k_draft_align_long  k_draft_align for members of 32768+ bases or V / U beyond the LDS: 32-bit cells in HBM
+//   k_draft_cns_deep    k_draft_cns for ladders of 65 .. 65535 members: 64-lane chunks, links numbered in global member order
 //
 // Everything is integer work on 2-bit bases; nothing here is GEMM-shaped.  Bound: latency (dependent look-ups along one
 // alignment path), hidden by running thousands of ladders' wavefronts side by side.
@@ -338,6 +340,287 @@ __global__ __launch_bounds__(64) void k_draft_cns(const DraftJob* __restrict__ j
                 for (int a = 0, b = len - 1; a < b; a++, b--) { const char c = o[a]; o[a] = o[b]; o[b] = c; }
             } else if (!cap_hit) {
                 atomicOr(status, DRAFT_ST_BASE);       // (the reference's assert(g_best_score != -1))
+            }
+            out_len[ld] = len;
+        }
+        __syncthreads();
+    }
+}
+
+// ---- long jobs: members of 32768+ bases, or V / U + staged sequences beyond the LDS ------------------------------
+// k_draft_align with 32-bit cells: V / U and both staged sequences in the job's stretch of dtab (behind its per-d table, see the
+// host's sizing), a (d, k) record as two words (x1 | came from k - 1 << 31 and x2 in full).  The rounds, the snake, the band, the
+// trace-back and the tags are k_draft_align's line by line.  Jobs jb_base .. jb_base + n_jobs - 1 (status[3] is the cursor).
+__global__ __launch_bounds__(64) void k_draft_align_long(const unsigned char* __restrict__ bps, const DraftJob* __restrict__ jobs, int jb_base, int n_jobs, int band_tol,
+                                                         unsigned* __restrict__ ents, int* __restrict__ dtab, unsigned* __restrict__ tags, int* __restrict__ n_tags,
+                                                         int* __restrict__ status) {
+    const int lane = threadIdx.x;
+    while (true) {
+        int jb = 0;
+        if (lane == 0) jb = atomicAdd(status + 3, 1);
+        jb = __builtin_amdgcn_readfirstlane(jb);
+        if (jb >= n_jobs) break;
+        jb += jb_base;
+        const DraftJob J = jobs[jb];
+        const int q_len = J.q.len, t_len = J.t.len, max_d = J.max_d;
+        int* __restrict__ DT = dtab + J.dtab_off;
+        int* V = DT + 2 * (max_d + 1);                                      // [2 * max_d + 2] each
+        int* U = V + (2 * max_d + 2);
+        unsigned* Wq = reinterpret_cast<unsigned*>(U + (2 * max_d + 2));
+        unsigned* Wt = Wq + draft_words(q_len);
+        for (int i = lane; i < 2 * (2 * max_d + 2); i += 64) V[i] = 0;
+        for (int i = lane; i < draft_words(q_len); i += 64) Wq[i] = draft_window(bps, J.q, 16 * i);
+        for (int i = lane; i < draft_words(t_len); i += 64) Wt[i] = draft_window(bps, J.t, 16 * i);
+        __syncthreads();
+        const int k_off = max_d, band_size = band_tol * 2;
+        unsigned* __restrict__ E = ents + J.ent_off;
+        unsigned* __restrict__ TG = tags + J.tag_off;
+        int best_m = -1, min_k = 0, max_k = 0;
+        long long n_ent = 0;
+        int fin_d = -1, fin_k = 0;
+        bool overflow = false;
+        for (int d = 0; d < max_d; d++) {
+            if (max_k - min_k > band_size) break;
+            const int nk = (max_k - min_k) / 2 + 1;
+            if (n_ent + nk > J.ent_cap) { overflow = true; break; }
+            if (lane == 0) { DT[2 * d] = (int)n_ent; DT[2 * d + 1] = min_k; }
+            int my_best = -1;
+            unsigned long long done_any = 0ull;
+            int done_at = 0;
+            for (int it = 0; it * 64 < nk && !done_any; it++) {
+                const int idx = it * 64 + lane;
+                const bool on = idx < nk;
+                const int k = min_k + 2 * idx;
+                int x = 0, y = 0;
+                bool fin = false;
+                if (on) {
+                    unsigned pre_minus;
+                    if (k == min_k || (k != max_k && V[k - 1 + k_off] < V[k + 1 + k_off])) { pre_minus = 0u; x = V[k + 1 + k_off]; }
+                    else { pre_minus = 1u; x = V[k - 1 + k_off] + 1; }
+                    y = x - k;
+                    const int x1 = x;
+                    while (true) {
+                        const int rem = min(q_len - x, t_len - y);
+                        if (rem <= 0) break;
+                        const unsigned df = draft_lds_window(Wq, x) ^ draft_lds_window(Wt, y);
+                        const int m = min(df ? (int)(__clz(df) >> 1) : 16, rem);
+                        x += m; y += m;
+                        if (m < 16) break;
+                    }
+                    E[2 * (n_ent + idx)] = (unsigned)x1;
+                    E[2 * (n_ent + idx) + 1] = (pre_minus << 31) | (unsigned)x;
+                    fin = x >= q_len || y >= t_len;
+                }
+                __syncthreads();            // (orders the reads of V above before the writes below; the fence makes them visible across lanes)
+                if (on) { V[k + k_off] = x; U[k + k_off] = x + y; my_best = max(my_best, x + y); }
+                done_any = __ballot(on && fin);
+                if (done_any) done_at = it * 64 + (int)__builtin_ctzll(done_any);
+                __syncthreads();
+            }
+            if (done_any) {
+                fin_d = d; fin_k = min_k + 2 * done_at;
+                n_ent += done_at + 1;
+                break;
+            }
+            n_ent += nk;
+            best_m = max(best_m, wave_max(my_best));
+            int lo = max_k, hi = min_k;
+            for (int c = 0; c * 64 < nk; c++) {
+                const int idx = c * 64 + lane;
+                const bool ok = idx < nk && U[min_k + 2 * idx + k_off] >= best_m - band_tol;
+                const unsigned long long Bm = __ballot(ok);
+                if (Bm) {
+                    lo = min(lo, min_k + 2 * (c * 64 + (int)__builtin_ctzll(Bm)));
+                    hi = max(hi, min_k + 2 * (c * 64 + 63 - (int)__builtin_clzll(Bm)));
+                }
+            }
+            max_k = hi + 1; min_k = lo - 1;
+            __syncthreads();
+        }
+        if (overflow && lane == 0) atomicOr(status, DRAFT_ST_CAP);
+        if (lane == 0) TG[0] = draft_tag(0, 0, 3);
+        long long n_col = 1;
+        if (fin_d >= 0 && !overflow) {
+            int* path = V;                  // V / U are no longer needed: the record index of every d on the path
+            __syncthreads();
+            if (lane == 0) {
+                int ck = fin_k;
+                for (int cd = fin_d; cd >= 0; cd--) {
+                    const int at = DT[2 * cd] + (ck - DT[2 * cd + 1]) / 2;
+                    path[cd] = at;
+                    ck = (E[2ll * at + 1] >> 31) ? ck - 1 : ck + 1;
+                }
+            }
+            __syncthreads();
+            int jj = 0, py = 0, px = 0;
+            bool bad_delta = false;
+            const long long col_cap = (long long)q_len + t_len + 2;
+            for (int cd = 0; cd <= fin_d; cd++) {
+                const long long at = path[cd];
+                const int x1 = (int)E[2 * at], x2 = (int)(E[2 * at + 1] & 0x7fffffffu);
+                if (cd > 0) {
+                    const bool x_step = E[2 * at + 1] >> 31;
+                    if (n_col + 1 > col_cap) { overflow = true; break; }
+                    if (x_step) {
+                        jj += 1;
+                        if (jj >= 255) bad_delta = true;
+                        if (lane == 0) TG[n_col] = draft_tag(py, jj & 255, draft_lds_base(Wq, px));
+                        px += 1;
+                    } else {
+                        jj = 0;
+                        py += 1;
+                        if (lane == 0) TG[n_col] = draft_tag(py, 0, 4);
+                    }
+                    n_col += 1;
+                }
+                const int run = x2 - x1;
+                if (run > 0) {
+                    if (n_col + run > col_cap) { overflow = true; break; }
+                    for (int t = lane; t < run; t += 64) TG[n_col + t] = draft_tag(py + 1 + t, 0, draft_lds_base(Wq, px + t));
+                    n_col += run; px += run; py += run; jj = 0;
+                }
+            }
+            if (lane == 0 && bad_delta) atomicOr(status, DRAFT_ST_DELTA);
+            if (lane == 0 && overflow) atomicOr(status, DRAFT_ST_CAP);
+        }
+        if (lane == 0) n_tags[jb] = (int)n_col;
+        __syncthreads();
+    }
+}
+
+// ---- ladders of 65 .. 65535 members ----------------------------------------------------------------------------
+// k_draft_cns over the members in 64-lane chunks, lane i of chunk c = member 64 c + i.  Per member a cursor in HBM (its next tag,
+// its last column); per column (t, delta) one pass over the chunks reads every member's next tag and leaves, per base, a mask of
+// the members that carry it (R, LDS); then per base the links are enumerated in GLOBAL member order - the lowest member not
+// counted yet names the next link, one pass over the chunks from its chunk on counts (and clears) the members with that link.
+// So a link's number is the lowest member index that carries it, as update_col numbers them (falcon.c tag loop), the counts are
+// the sums over the chunks, and the strict `score > best` breaks ties as k_draft_cns does.  Everything else - scores, S2 / S2F,
+// the best-predecessor table, the trace-back with its link-index quirk - is k_draft_cns'.
+struct DraftMember { long long p, end; unsigned prev; int pad; };
+
+__global__ __launch_bounds__(64) void k_draft_cns_deep(const DraftJob* __restrict__ jobs, const DraftLadder* __restrict__ ladders, int n_ladders, const unsigned* __restrict__ tags,
+                                                       const int* __restrict__ n_tags, unsigned* __restrict__ cols, int* __restrict__ tbase, char* __restrict__ out,
+                                                       int* __restrict__ out_len, unsigned min_cov, int* __restrict__ status, int* __restrict__ s2_far,
+                                                       DraftMember* __restrict__ mstate, unsigned* __restrict__ mlink) {
+    __shared__ int S2[2][DRAFT_S2_LDS][5];
+    extern __shared__ unsigned long long R[];     // [5][chunks]: the launch's largest ladder sets the size
+    int* __restrict__ const S2F = s2_far + (size_t)blockIdx.x * (2 * 256 * 5);
+    const int lane = threadIdx.x;
+    while (true) {
+        int ld = 0;
+        if (lane == 0) ld = atomicAdd(status + 4, 1);
+        ld = __builtin_amdgcn_readfirstlane(ld);
+        if (ld >= n_ladders) break;
+        const DraftLadder L = ladders[ld];
+        const int nc = (L.n + 63) / 64;
+        // a lane reads and writes the state of its own members only (64 c + lane): no ordering across lanes is needed for it
+        DraftMember* __restrict__ MS = mstate + L.job0;
+        unsigned* __restrict__ ML = mlink + L.job0;         // the link (previous column) of a member whose tag is at the current column
+        for (int m = lane; m < L.n; m += 64) {
+            const long long o = jobs[L.job0 + m].tag_off;
+            MS[m] = DraftMember{o, o + n_tags[L.job0 + m], DRAFT_NONE, 0};
+        }
+        unsigned* __restrict__ C = cols + L.col_off;
+        int* __restrict__ TB = tbase + L.tb_off;
+        int slot = 0;
+        int g_best = -2, g_ck = 0, g_t = 0;
+        unsigned g_col = DRAFT_NONE;
+        int best_ck = -1;
+        bool cap_hit = false;
+        for (int t = 0; t < L.t_len; t++) {
+            int cov = 0;
+            if (lane == 0) TB[2 * t] = slot;
+            for (int delta = 0;; delta++) {
+                // the members' next tags: who is at (t, delta), with which base; their cursors move on
+                int h = 0;
+                for (int c = 0; c < nc; c++) {
+                    const int m = c * 64 + lane;
+                    bool has = false;
+                    int base = 7;
+                    if (m < L.n) {
+                        const DraftMember st = MS[m];
+                        const unsigned tg = st.p < st.end ? tags[st.p] : DRAFT_NONE;
+                        has = tg != DRAFT_NONE && (int)(tg >> 11) == t && (int)((tg >> 3) & 255u) == delta;
+                        if (has) {
+                            base = (int)(tg & 7u);
+                            ML[m] = st.prev;
+                            MS[m] = DraftMember{st.p + 1, st.end, tg, 0};
+                        }
+                    }
+                    h += __popcll(__ballot(has));
+                    for (int kk = 0; kk < 5; kk++) {
+                        const unsigned long long B = __ballot(base == kk);
+                        if (lane == 0) R[kk * nc + c] = B;
+                    }
+                }
+                if (delta == 0) { cov = h; if (lane == 0) TB[2 * t + 1] = cov; }
+                if (!h) break;
+                if ((slot + 1) * 5 > L.col_cap || delta > 255) { cap_hit = true; break; }
+                __syncthreads();
+                for (int kk = 0; kk < 5; kk++) {
+                    int best = -2;
+                    unsigned best_p = 0u;
+                    int ck = 0;
+                    int c0 = 0;
+                    while (true) {
+                        while (c0 < nc && R[kk * nc + c0] == 0ull) c0++;
+                        if (c0 == nc) break;
+                        const int lead = (int)__builtin_ctzll(R[kk * nc + c0]);
+                        unsigned lp = 0u;
+                        int cnt = 0;
+                        for (int c = c0; c < nc; c++) {
+                            const unsigned long long Mc = R[kk * nc + c];
+                            if (!Mc) continue;
+                            const bool mine = (Mc >> lane) & 1ull;
+                            const unsigned pv = mine ? ML[c * 64 + lane] : DRAFT_NONE;
+                            if (c == c0) lp = __shfl(pv, lead);
+                            const unsigned long long same = __ballot(mine && pv == lp);
+                            cnt += __popcll(same);
+                            if (lane == 0) R[kk * nc + c] = Mc & ~same;
+                            __syncthreads();
+                        }
+                        int ls = 0;
+                        if (lp != DRAFT_NONE) {
+                            const unsigned pt = (lp >> 11) & 1u, pd = (lp >> 3) & 255u, pb = lp & 7u;
+                            ls = pd < (unsigned)DRAFT_S2_LDS ? S2[pt][pd][pb] : S2F[(pt * 256 + pd) * 5 + pb];
+                        }
+                        const int score = ls + 2 * cnt - cov;
+                        if (score > best) { best = score; best_p = lp; best_ck = ck; }
+                        ck++;
+                    }
+                    if (lane == 0) {
+                        if (delta < DRAFT_S2_LDS) S2[t & 1][delta][kk] = best; else S2F[((t & 1) * 256 + delta) * 5 + kk] = best;
+                        C[slot * 5 + kk] = best_p;
+                    }
+                    if (best > g_best) { g_best = best; g_col = (unsigned)(slot * 5 + kk); g_ck = best_ck; g_t = t; }
+                }
+                __syncthreads();
+                slot++;
+            }
+            if (cap_hit) break;
+        }
+        if (cap_hit && lane == 0) atomicOr(status, DRAFT_ST_CAP);
+        // ---- the sequence, back to front (falcon.c:440-478), then turned around: k_draft_cns' trace-back ------------------------
+        int len = 0;
+        if (lane == 0) {
+            char* __restrict__ o = out + L.out_off;
+            if (g_col != DRAFT_NONE && !cap_hit) {
+                char bb = '$';
+                int ck = g_ck, i = g_t;
+                unsigned col = g_col;
+                while (true) {
+                    if (ck >= 0 && ck < 5) bb = (unsigned)TB[2 * i + 1] > min_cov ? "ACGT-"[ck] : "acgt-"[ck];
+                    const unsigned bp = C[col];
+                    if (bp == DRAFT_NONE || len >= 2 * L.t_len) break;
+                    i = (int)(bp >> 11);
+                    const int j = (int)((bp >> 3) & 255u);
+                    ck = (int)(bp & 7u);
+                    col = (unsigned)((TB[2 * i] + j) * 5 + ck);
+                    if (bb != '-') o[len++] = bb;
+                }
+                for (int a = 0, b = len - 1; a < b; a++, b--) { const char c = o[a]; o[a] = o[b]; o[b] = c; }
+            } else if (!cap_hit) {
+                atomicOr(status, DRAFT_ST_BASE);
             }
             out_len[ld] = len;
         }

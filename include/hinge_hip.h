@@ -378,18 +378,20 @@ int hinge_draft_mappings(hinge_ctx* ctx, int64_t n_aln, const hinge_cns_alignmen
                          const int64_t* map_off, uint32_t* mapping);
 /* One member of a ladder: bases [start, end) of read `read` in its strand frame (strand 1: of its reverse complement). */
 typedef struct hinge_draft_rung { int32_t read, strand, start, end; } hinge_draft_rung;
-/* hinge_draft_ladders: for every ladder (members rungs[rung_off[l] .. rung_off[l + 1]), 1 .. 64 of them) the consensus of
+/* hinge_draft_ladders: for every ladder (members rungs[rung_off[l] .. rung_off[l + 1]), 1 .. 65535 of them) the consensus of
  *   draft.cpp:597-691: every member aligned to member template_rung[l] with falcon's banded O(ND) aligner (lib/DW_banded.c:97-311,
  *   band_tolerance = 150 in the reference), alignment tags with a leading 'T' column (lib/falcon.c:68-125), get_cns_from_align_tags
  *   over template length + 1 positions with min_cov 1 (lib/falcon.c:246-517) - ties, the link-index quirk of its last base and the
  *   lower case of thinly covered bases included.  out_off[l] = where ladder l's string goes in `out` (caller-laid-out slots of at
  *   least 2 * (template length + 1) bytes: out_off[n_ladders] = the buffer's size), out_len[l] = its length.
- *   Limits (the reference has none; draft.cpp's ladders are `[draft] tspace` ~ 900-base windows at the data set's coverage):
- *   HINGE_E_CAPACITY: more than 64 members (one lane per member in the vote), a member of 32768+ bases, or member + template beyond
- *   ~61 000 bases together (the aligner's V / U arrays - 16-bit cells, 8 x 0.3 x (q + t) bytes - and both sequences at 2 bits per base
- *   live in the CU's 160 KB of LDS); HINGE_E_RANGE: 255+
- *   inserted bases in a row (the reference's tags are undefined there, falcon.c:96); HINGE_E_UNDEFINED: its assert(g_best_score != -1).
- *   Any of them fails the CALL (all ladders): `draft_assembly` stops as the reference does on its own asserts. */
+ *   Limits: every ladder the reference answers is answered, whatever its depth or member length (ladders of up to 64 members
+ *   with members below 32768 bases whose member + template fit the aligner's LDS take the first kernels; deeper ladders and longer
+ *   members take k_draft_cns_deep / k_draft_align_long), within two bounds of the reference's own data types:
+ *   HINGE_E_CAPACITY for a ladder of 0 or 65536+ members (the reference's link_count / count / n_link are uint16_t, common.h: its
+ *   vote wraps there) and for a template of 2^21 or more bases (an alignment tag holds its template position in 21 bits).
+ *   Reference-undefined input: HINGE_E_RANGE for 255+ inserted bases in a row (the reference's tags are undefined there,
+ *   falcon.c:96); HINGE_E_UNDEFINED for its assert(g_best_score != -1).  Any of them fails the CALL (all ladders): `draft_assembly`
+ *   stops as the reference does on its own asserts. */
 int hinge_draft_ladders(hinge_ctx* ctx, int64_t n_ladders, const int64_t* rung_off, const hinge_draft_rung* rungs, const int32_t* template_rung, int32_t band_tolerance,
                         const int64_t* out_off, char* out, int32_t* out_len);
 
