@@ -9,14 +9,18 @@
 //                   template (DW_banded.c:97-311) - the diagonals of one d across the lanes, V / U in LDS, the (d, k) records 4 bytes
 //                   each in HBM, the trace-back by lane 0, then the alignment tags (falcon.c:68-125, with the leading 'T' column of
 //                   draft.cpp:646-655) written run by run, a run's columns across the lanes
+//   k_draft_align_long  the same for members of 32768+ bases or V / U beyond the LDS: 32-bit cells in HBM.  Both are
+//                   ONE body, draft_align<P>.  The cell policies DraftCellsLds / DraftCellsHbm hold what differs: where a job's
+//                   V / U / staged sequences live and how wide a cell is, how a (d, k) record is packed, which cursor draws the
+//                   jobs.  The host sizes a job's scratch with the same policies (draft_capi.inc)
 //   k_draft_cns     one WAVEFRONT per ladder, one LANE per member: falcon's consensus over the members' tags (falcon.c:246-517) -
 //                   the columns (t_pos, delta, base) are visited in the reference's order, the members that share a column vote with
 //                   ballots (a link = the member's previous column; equal links are found with readlane + ballot, in member order =
 //                   the reference's insertion order, so ties fall the same way), scores as doubled integers (the reference adds
 //                   link counts and halves of the coverage: exact in either form), the best-predecessor table in HBM, the
 //                   trace-back by lane 0 - including the reference's habit of deciding the LAST base by a link index
-//   k_draft_align_long  k_draft_align for members of 32768+ bases or V / U beyond the LDS: 32-bit cells in HBM
-//   k_draft_cns_deep    k_draft_cns for ladders of 65 .. 65535 members: 64-lane chunks, links numbered in global member order
+//   k_draft_cns_deep    k_draft_cns for ladders of 65 .. 65535 members: 64-lane chunks, links numbered in global member order.  The
+//                   voting is its own; the score store (draft_s2_put) and the trace-back (draft_cns_emit) are shared
 //
 // Everything is integer work on 2-bit bases; nothing here is GEMM-shaped.  Bound: latency (dependent look-ups along one
 // alignment path), hidden by running thousands of ladders' wavefronts side by side.
@@ -53,6 +57,11 @@ __device__ __forceinline__ unsigned draft_lds_window(const unsigned* W, int x) {
     return (unsigned)((two << (2 * (x & 15))) >> 32);
 }
 __device__ __forceinline__ int draft_lds_base(const unsigned* W, int x) { return (int)((W[x >> 4] >> (30 - 2 * (x & 15))) & 3u); }
+// stages a sequence across the lanes: the words that start inside it from draft_window, the spare word 0 - nothing is loaded from a
+// window at or past the sequence's end (behind the last read of the base buffer that is memory nobody allocated)
+__device__ __forceinline__ void draft_stage(unsigned* W, const unsigned char* __restrict__ bps, const DraftSeq& s, int lane) {
+    for (int i = lane; i < draft_words(s.len); i += 64) W[i] = 16 * i < s.len ? draft_window(bps, s, 16 * i) : 0u;
+}
 
 constexpr unsigned DRAFT_GAP = 0x80000000u;
 
@@ -81,50 +90,99 @@ struct DraftJob {
 constexpr int DRAFT_ST_CAP = 1;      // a record / tag buffer too small (host sizing bug)
 constexpr int DRAFT_ST_DELTA = 2;    // a run of 255+ inserted bases: the reference's tags are undefined there (falcon.c:96)
 constexpr int DRAFT_ST_BASE = 4;
+// the words of `status`: the DRAFT_ST_* flags of a call, then one cursor per kernel that draws its work (cleared per batch)
+enum { DRAFT_SLOT_FLAGS, DRAFT_SLOT_ALIGN, DRAFT_SLOT_CNS, DRAFT_SLOT_ALIGN_LONG, DRAFT_SLOT_CNS_DEEP, DRAFT_SLOTS };
 
 // a tag: t_pos << 11 | delta << 3 | base (0-3 A C G T, 4 '-')
 __device__ __forceinline__ unsigned draft_tag(int t_pos, int delta, int base) { return ((unsigned)t_pos << 11) | ((unsigned)delta << 3) | (unsigned)base; }
 
-__global__ __launch_bounds__(64) void k_draft_align(const unsigned char* __restrict__ bps, const DraftJob* __restrict__ jobs, int n_jobs, int band_tol,
-                                                    unsigned* __restrict__ ents, int* __restrict__ dtab, unsigned* __restrict__ tags, int* __restrict__ n_tags,
-                                                    int* __restrict__ status) {
-    extern __shared__ int lds[];
+__host__ __device__ inline int draft_dtab_words(int max_d) { return 2 * (max_d + 1); }      // a job's per-d table (DraftJob::dtab_off)
+
+// A job's scratch, the ONE place that lays it out - the kernels place it, the host sizes it with words(): V and U, [2 * max_d + 2]
+// cells each, then both sequences staged 16 bases per word.  The trace-back's path (the record index of every d on it: at most max_d
+// ints) reuses the V / U words, which nobody needs by then.
+template <class Cell> struct DraftScratch {
+    Cell *V, *U;
+    unsigned *Wq, *Wt;
+    int* vu;                    // the V / U words as ints: cleared at the start of a job, the path's at its end
+    int n_vu;
+    __host__ __device__ static int vu_words(int max_d) { return 2 * (2 * max_d + 2) * (int)sizeof(Cell) / (int)sizeof(int); }
+    __host__ __device__ static int words(int max_d, int q_len, int t_len) { return vu_words(max_d) + draft_words(q_len) + draft_words(t_len); }
+    __device__ __forceinline__ DraftScratch(int* at, int max_d, int q_len)
+        : V(reinterpret_cast<Cell*>(at)), U(V + (2 * max_d + 2)), Wq(reinterpret_cast<unsigned*>(at + vu_words(max_d))), Wt(Wq + draft_words(q_len)), vu(at), n_vu(vu_words(max_d)) {}
+};
+struct DraftRec { int x1, x2; bool x_step; };      // a (d, k) record: the snake x1 .. x2, reached from k - 1 (a query base against a gap)
+
+// The two cell policies of draft_align: what k_draft_align and k_draft_align_long differ in, and nothing else.
+// V / U as 16-bit cells in LDS (x < 32768: a member has fewer bases; x + y < 65536): half the LDS of 32-bit cells, i.e. twice the
+// wavefronts per CU for a kernel whose wavefronts wait half their cycles (a latency chain per round).  A record is one word:
+// x1 (15 bits) | came from k - 1 | x2 (16 bits).
+struct DraftCellsLds {
+    typedef unsigned short cell;
+    typedef int count;                                        // records and columns of a job
+    typedef DraftScratch<cell> scratch;
+    static constexpr int CURSOR = DRAFT_SLOT_ALIGN, REC_WORDS = 1;
+    __device__ __forceinline__ static scratch place(int* lds, int* DT, int max_d, int q_len) { return scratch(lds, max_d, q_len); }
+    __device__ __forceinline__ static void put(unsigned* __restrict__ E, count at, int x1, unsigned pre_minus, int x2) { E[at] = ((unsigned)x1 << 17) | (pre_minus << 16) | (unsigned)x2; }
+    __device__ __forceinline__ static DraftRec get(const unsigned* __restrict__ E, count at) { const unsigned e = E[at]; return DraftRec{(int)(e >> 17), (int)(e & 0xffffu), (bool)((e >> 16) & 1u)}; }
+    __device__ __forceinline__ static bool x_step(const unsigned* __restrict__ E, count at) { return (E[at] >> 16) & 1u; }
+};
+// Long jobs (members of 32768+ bases, or a scratch beyond the LDS): 32-bit cells, the scratch in the job's stretch of
+// dtab behind its per-d table, a record as two words (x1, then came from k - 1 << 31 | x2), 64-bit record and column counts.
+struct DraftCellsHbm {
+    typedef int cell;
+    typedef long long count;
+    typedef DraftScratch<cell> scratch;
+    static constexpr int CURSOR = DRAFT_SLOT_ALIGN_LONG, REC_WORDS = 2;
+    __device__ __forceinline__ static scratch place(int* lds, int* DT, int max_d, int q_len) { return scratch(DT + draft_dtab_words(max_d), max_d, q_len); }
+    __device__ __forceinline__ static void put(unsigned* __restrict__ E, count at, int x1, unsigned pre_minus, int x2) { E[2 * at] = (unsigned)x1; E[2 * at + 1] = (pre_minus << 31) | (unsigned)x2; }
+    __device__ __forceinline__ static DraftRec get(const unsigned* __restrict__ E, count at) { const unsigned w = E[2 * at + 1]; return DraftRec{(int)E[2 * at], (int)(w & 0x7fffffffu), (bool)(w >> 31)}; }
+    __device__ __forceinline__ static bool x_step(const unsigned* __restrict__ E, count at) { return E[2 * at + 1] >> 31; }
+};
+
+// Jobs jb_base .. jb_base + n_jobs - 1, one wavefront each.  `lds` is the launch's dynamic LDS where the policy keeps its cells there.
+template <class P>
+__device__ __forceinline__ void draft_align(int* lds, const unsigned char* __restrict__ bps, const DraftJob* __restrict__ jobs, int jb_base, int n_jobs, int band_tol,
+                                            unsigned* __restrict__ ents, int* __restrict__ dtab, unsigned* __restrict__ tags, int* __restrict__ n_tags, int* __restrict__ status) {
+    typedef typename P::cell cell;
+    typedef typename P::count count;
     const int lane = threadIdx.x;
-    // jobs are DRAWN (status[1] is the cursor, zero at launch): an alignment's time follows its edit distance - the template against
-    // itself is over at d = 0, a diverged member takes 250 rounds - and with a fixed stride the launch waited for its unluckiest
-    // wavefront at twice the mean (SQ_WAVE_CYCLES / waves = 51 % of the launch, profiles/r6f_draft_*)
+    // jobs are DRAWN (status[P::CURSOR] is the cursor, zero at launch): an alignment's time follows its edit distance - the template
+    // against itself is over at d = 0, a diverged member takes 250 rounds - and with a fixed stride the launch waited for its
+    // unluckiest wavefront at twice the mean (SQ_WAVE_CYCLES / waves = 51 % of the launch, profiles/r6f_draft_*)
     while (true) {
         int jb = 0;
-        if (lane == 0) jb = atomicAdd(status + 1, 1);
+        if (lane == 0) jb = atomicAdd(status + P::CURSOR, 1);
         jb = __builtin_amdgcn_readfirstlane(jb);
         if (jb >= n_jobs) break;
+        jb += jb_base;
         const DraftJob J = jobs[jb];
         const int q_len = J.q.len, t_len = J.t.len, max_d = J.max_d;
-        // V / U as 16-bit cells (x < 32768: a member has fewer bases; x + y < 65536): half the LDS of 32-bit cells, i.e. twice the
-        // wavefronts per CU for a kernel whose wavefronts wait half their cycles (a latency chain per round)
-        unsigned short* V = reinterpret_cast<unsigned short*>(lds);                 // [2 * max_d + 1]
-        unsigned short* U = V + (2 * max_d + 2);
-        // Round 6: both sequences staged in LDS, 16 bases per word in their own frame (strand applied once here, not per base), so a
-        // snake compares 16 base pairs per step - two LDS words per side, one XOR, one count of leading zeros - instead of two
+        int* __restrict__ DT = dtab + J.dtab_off;
+        const typename P::scratch S = P::place(lds, DT, max_d, q_len);
+        cell* const V = S.V;
+        cell* const U = S.U;
+        // Round 6: both sequences staged, 16 bases per word in their own frame (strand applied once here, not per base), so a
+        // snake compares 16 base pairs per step - two staged words per side, one XOR, one count of leading zeros - instead of two
         // dependent byte loads from global memory per base pair (12 % errors: a snake is ~8 bases, i.e. ONE step).
-        unsigned* Wq = reinterpret_cast<unsigned*>(lds + (2 * max_d + 2));
-        unsigned* Wt = Wq + draft_words(q_len);
-        for (int i = lane; i < 2 * max_d + 2; i += 64) lds[i] = 0;
-        for (int i = lane; i < draft_words(q_len); i += 64) Wq[i] = draft_window(bps, J.q, 16 * i);
-        for (int i = lane; i < draft_words(t_len); i += 64) Wt[i] = draft_window(bps, J.t, 16 * i);
+        unsigned* const Wq = S.Wq;
+        unsigned* const Wt = S.Wt;
+        for (int i = lane; i < S.n_vu; i += 64) S.vu[i] = 0;
+        draft_stage(Wq, bps, J.q, lane);
+        draft_stage(Wt, bps, J.t, lane);
         __syncthreads();
         const int k_off = max_d, band_size = band_tol * 2;
         unsigned* __restrict__ E = ents + J.ent_off;
-        int* __restrict__ DT = dtab + J.dtab_off;
         unsigned* __restrict__ TG = tags + J.tag_off;
-        int best_m = -1, min_k = 0, max_k = 0, n_ent = 0;
+        int best_m = -1, min_k = 0, max_k = 0;
+        count n_ent = 0;
         int fin_d = -1, fin_k = 0;
         bool overflow = false;
         for (int d = 0; d < max_d; d++) {
             if (max_k - min_k > band_size) break;
             const int nk = (max_k - min_k) / 2 + 1;
             if (n_ent + nk > J.ent_cap) { overflow = true; break; }
-            if (lane == 0) { DT[2 * d] = n_ent; DT[2 * d + 1] = min_k; }
+            if (lane == 0) { DT[2 * d] = (int)n_ent; DT[2 * d + 1] = min_k; }
             int my_best = -1;
             unsigned long long done_any = 0ull;
             int done_at = 0;
@@ -148,11 +206,11 @@ __global__ __launch_bounds__(64) void k_draft_align(const unsigned char* __restr
                         x += m; y += m;
                         if (m < 16) break;
                     }
-                    E[n_ent + idx] = ((unsigned)x1 << 17) | (pre_minus << 16) | (unsigned)x;      // x1 (15 bits) | came from k - 1 | x2 (16 bits)
+                    P::put(E, n_ent + idx, x1, pre_minus, x);
                     fin = x >= q_len || y >= t_len;
                 }
-                __syncthreads();            // (one wavefront: orders the LDS reads above before the writes below)
-                if (on) { V[k + k_off] = (unsigned short)x; U[k + k_off] = (unsigned short)(x + y); my_best = max(my_best, x + y); }
+                __syncthreads();            // (one wavefront: orders the reads of V above before the writes below; for cells in HBM its fence makes them visible across lanes)
+                if (on) { V[k + k_off] = (cell)x; U[k + k_off] = (cell)(x + y); my_best = max(my_best, x + y); }
                 done_any = __ballot(on && fin);
                 if (done_any) done_at = it * 64 + (int)__builtin_ctzll(done_any);
                 __syncthreads();
@@ -179,20 +237,20 @@ __global__ __launch_bounds__(64) void k_draft_align(const unsigned char* __restr
             max_k = hi + 1; min_k = lo - 1;
             __syncthreads();
         }
-        if (overflow && lane == 0) atomicOr(status, DRAFT_ST_CAP);
+        if (overflow && lane == 0) atomicOr(status + DRAFT_SLOT_FLAGS, DRAFT_ST_CAP);
         // ---- tags: the leading 'T' column, then the path's columns (falcon.c:68-125 on the rows of DW_banded.c:245-300) ---------------
         if (lane == 0) TG[0] = draft_tag(0, 0, 3);
-        int n_col = 1;
+        count n_col = 1;
         if (fin_d >= 0 && !overflow) {
-            // trace-back: record index of every d on the path, kept in the V / U space of LDS (no longer needed; d <= 2 * max_d ints)
-            int* path = lds;
+            // trace-back: record index of every d on the path, kept in the V / U words (no longer needed; d < max_d ints)
+            int* path = S.vu;
             __syncthreads();
             if (lane == 0) {
                 int ck = fin_k;
                 for (int cd = fin_d; cd >= 0; cd--) {
                     const int at = DT[2 * cd] + (ck - DT[2 * cd + 1]) / 2;
                     path[cd] = at;
-                    ck = ((E[at] >> 16) & 1u) ? ck - 1 : ck + 1;
+                    ck = P::x_step(E, at) ? ck - 1 : ck + 1;
                 }
             }
             __syncthreads();
@@ -200,15 +258,12 @@ __global__ __launch_bounds__(64) void k_draft_align(const unsigned char* __restr
             int py = 0;                     // target bases consumed so far
             int px = 0;
             bool bad_delta = false;
+            const count col_cap = (count)q_len + t_len + 2;
             for (int cd = 0; cd <= fin_d; cd++) {
-                const unsigned e = E[path[cd]];
-                const int x1 = (int)(e >> 17), x2 = (int)(e & 0xffffu);
-                const int k = x1 - 0;       // (y1 follows from the step kind below)
-                (void)k;
-                if (cd > 0) {               // the edit step from (px, py): one column
-                    const bool x_step = (e >> 16) & 1u;          // came from k - 1: a query base against a gap
-                    if (n_col + 1 > q_len + t_len + 2) { overflow = true; break; }
-                    if (x_step) {
+                const DraftRec e = P::get(E, path[cd]);
+                if (cd > 0) {               // the edit step from (px, py): one column (y1 follows from the step kind)
+                    if (n_col + 1 > col_cap) { overflow = true; break; }
+                    if (e.x_step) {              // came from k - 1: a query base against a gap
                         jj += 1;
                         if (jj >= 255) bad_delta = true;
                         if (lane == 0) TG[n_col] = draft_tag(py, jj & 255, draft_lds_base(Wq, px));
@@ -220,19 +275,32 @@ __global__ __launch_bounds__(64) void k_draft_align(const unsigned char* __restr
                     }
                     n_col += 1;
                 }
-                const int run = x2 - x1;    // the snake: run matched pairs
+                const int run = e.x2 - e.x1;  // the snake: run matched pairs
                 if (run > 0) {
-                    if (n_col + run > q_len + t_len + 2) { overflow = true; break; }
+                    if (n_col + run > col_cap) { overflow = true; break; }
                     for (int t = lane; t < run; t += 64) TG[n_col + t] = draft_tag(py + 1 + t, 0, draft_lds_base(Wq, px + t));
                     n_col += run; px += run; py += run; jj = 0;
                 }
             }
-            if (lane == 0 && bad_delta) atomicOr(status, DRAFT_ST_DELTA);
-            if (lane == 0 && overflow) atomicOr(status, DRAFT_ST_CAP);
+            if (lane == 0 && bad_delta) atomicOr(status + DRAFT_SLOT_FLAGS, DRAFT_ST_DELTA);
+            if (lane == 0 && overflow) atomicOr(status + DRAFT_SLOT_FLAGS, DRAFT_ST_CAP);
         }
-        if (lane == 0) n_tags[jb] = n_col;
+        if (lane == 0) n_tags[jb] = (int)n_col;
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(64) void k_draft_align(const unsigned char* __restrict__ bps, const DraftJob* __restrict__ jobs, int n_jobs, int band_tol,
+                                                    unsigned* __restrict__ ents, int* __restrict__ dtab, unsigned* __restrict__ tags, int* __restrict__ n_tags,
+                                                    int* __restrict__ status) {
+    extern __shared__ int lds[];
+    draft_align<DraftCellsLds>(lds, bps, jobs, 0, n_jobs, band_tol, ents, dtab, tags, n_tags, status);
+}
+// jobs jb_base .. jb_base + n_jobs - 1: in a batch the long ladders' jobs lie behind the short ones'
+__global__ __launch_bounds__(64) void k_draft_align_long(const unsigned char* __restrict__ bps, const DraftJob* __restrict__ jobs, int jb_base, int n_jobs, int band_tol,
+                                                         unsigned* __restrict__ ents, int* __restrict__ dtab, unsigned* __restrict__ tags, int* __restrict__ n_tags,
+                                                         int* __restrict__ status) {
+    draft_align<DraftCellsHbm>(nullptr, bps, jobs, jb_base, n_jobs, band_tol, ents, dtab, tags, n_tags, status);
 }
 
 // ---- falcon's consensus, one wavefront per ladder ---------------------------------------------------------------------------
@@ -247,6 +315,43 @@ struct DraftLadder {
 constexpr unsigned DRAFT_NONE = 0xffffffffu;
 constexpr int DRAFT_S2_LDS = 32;     // deltas (consecutive inserted bases in front of a template position) whose column scores live in LDS
 
+// where the column (t, delta, base) leaves its doubled score: the current and the previous template position are kept, by parity.
+// (The look-up of a predecessor's score - the same index from a tag word - stays written out in the two kernels: as a shared function
+// it changed k_draft_cns_deep's instruction order and cost it 2.3 %, profiles/r8a_draft_refactor_ab.json.)
+__device__ __forceinline__ void draft_s2_put(int (*S2)[DRAFT_S2_LDS][5], int* __restrict__ S2F, int t, int delta, int base, int score) {
+    // (the LDS store through an LDS-typed pointer: two stores of one value through generic pointers are folded into ONE flat store at
+    // a selected address - five of them per column in k_draft_cns - where the kernels had a ds_write and a global store)
+    typedef __attribute__((address_space(3))) int lds_int;
+    if (delta < DRAFT_S2_LDS) *(lds_int*)&S2[t & 1][delta][base] = score; else S2F[((t & 1) * 256 + delta) * 5 + base] = score;
+}
+
+// The sequence of a ladder, back to front from its best column (falcon.c:440-478), then turned around; returns its length.  One lane.
+// C = the best-predecessor table, TB = per t its first slot and coverage, (g_col, g_ck, g_t) = the best column, the LINK index its
+// score came from - the reference decides the last base by it - and its template position.
+__device__ __forceinline__ int draft_cns_emit(const DraftLadder& L, const unsigned* __restrict__ C, const int* __restrict__ TB, char* __restrict__ o, unsigned g_col, int g_ck,
+                                              int g_t, bool cap_hit, unsigned min_cov, int* __restrict__ status) {
+    int len = 0;
+    if (g_col != DRAFT_NONE && !cap_hit) {
+        char bb = '$';
+        int ck = g_ck, i = g_t;
+        unsigned col = g_col;
+        while (true) {
+            if (ck >= 0 && ck < 5) bb = (unsigned)TB[2 * i + 1] > min_cov ? "ACGT-"[ck] : "acgt-"[ck];
+            const unsigned bp = C[col];
+            if (bp == DRAFT_NONE || len >= 2 * L.t_len) break;
+            i = (int)(bp >> 11);
+            const int j = (int)((bp >> 3) & 255u);
+            ck = (int)(bp & 7u);
+            col = (unsigned)((TB[2 * i] + j) * 5 + ck);
+            if (bb != '-') o[len++] = bb;
+        }
+        for (int a = 0, b = len - 1; a < b; a++, b--) { const char c = o[a]; o[a] = o[b]; o[b] = c; }
+    } else if (!cap_hit) {
+        atomicOr(status + DRAFT_SLOT_FLAGS, DRAFT_ST_BASE);       // (the reference's assert(g_best_score != -1))
+    }
+    return len;
+}
+
 __global__ __launch_bounds__(64) void k_draft_cns(const DraftJob* __restrict__ jobs, const DraftLadder* __restrict__ ladders, int n_ladders, const unsigned* __restrict__ tags,
                                                   const int* __restrict__ n_tags, unsigned* __restrict__ cols, int* __restrict__ tbase, char* __restrict__ out,
                                                   int* __restrict__ out_len, unsigned min_cov, int* __restrict__ status, int* __restrict__ s2_far) {
@@ -256,9 +361,9 @@ __global__ __launch_bounds__(64) void k_draft_cns(const DraftJob* __restrict__ j
     __shared__ int S2[2][DRAFT_S2_LDS][5];
     int* __restrict__ const S2F = s2_far + (size_t)blockIdx.x * (2 * 256 * 5);
     const int lane = threadIdx.x;
-    while (true) {                           // ladders are drawn (status[2], zero at launch): their times differ with their members
+    while (true) {                           // ladders are drawn (status[DRAFT_SLOT_CNS], zero at launch): their times differ with their members
         int ld = 0;
-        if (lane == 0) ld = atomicAdd(status + 2, 1);
+        if (lane == 0) ld = atomicAdd(status + DRAFT_SLOT_CNS, 1);
         ld = __builtin_amdgcn_readfirstlane(ld);
         if (ld >= n_ladders) break;
         const DraftLadder L = ladders[ld];
@@ -307,7 +412,7 @@ __global__ __launch_bounds__(64) void k_draft_cns(const DraftJob* __restrict__ j
                         M &= ~same;
                     }
                     if (lane == 0) {
-                        if (delta < DRAFT_S2_LDS) S2[t & 1][delta][kk] = best; else S2F[((t & 1) * 256 + delta) * 5 + kk] = best;
+                        draft_s2_put(S2, S2F, t, delta, kk, best);
                         C[slot * 5 + kk] = best_p;
                     }
                     if (best > g_best) { g_best = best; g_col = (unsigned)(slot * 5 + kk); g_ck = best_ck; g_t = t; }
@@ -318,172 +423,8 @@ __global__ __launch_bounds__(64) void k_draft_cns(const DraftJob* __restrict__ j
             }
             if (cap_hit) break;
         }
-        if (cap_hit && lane == 0) atomicOr(status, DRAFT_ST_CAP);
-        // ---- the sequence, back to front (falcon.c:440-478), then turned around ----------------------------------------------------
-        int len = 0;
-        if (lane == 0) {
-            char* __restrict__ o = out + L.out_off;
-            if (g_col != DRAFT_NONE && !cap_hit) {
-                char bb = '$';
-                int ck = g_ck, i = g_t;
-                unsigned col = g_col;
-                while (true) {
-                    if (ck >= 0 && ck < 5) bb = (unsigned)TB[2 * i + 1] > min_cov ? "ACGT-"[ck] : "acgt-"[ck];
-                    const unsigned bp = C[col];
-                    if (bp == DRAFT_NONE || len >= 2 * L.t_len) break;
-                    i = (int)(bp >> 11);
-                    const int j = (int)((bp >> 3) & 255u);
-                    ck = (int)(bp & 7u);
-                    col = (unsigned)((TB[2 * i] + j) * 5 + ck);
-                    if (bb != '-') o[len++] = bb;
-                }
-                for (int a = 0, b = len - 1; a < b; a++, b--) { const char c = o[a]; o[a] = o[b]; o[b] = c; }
-            } else if (!cap_hit) {
-                atomicOr(status, DRAFT_ST_BASE);       // (the reference's assert(g_best_score != -1))
-            }
-            out_len[ld] = len;
-        }
-        __syncthreads();
-    }
-}
-
-// ---- long jobs: members of 32768+ bases, or V / U + staged sequences beyond the LDS ------------------------------
-// k_draft_align with 32-bit cells: V / U and both staged sequences in the job's stretch of dtab (behind its per-d table, see the
-// host's sizing), a (d, k) record as two words (x1 | came from k - 1 << 31 and x2 in full).  The rounds, the snake, the band, the
-// trace-back and the tags are k_draft_align's line by line.  Jobs jb_base .. jb_base + n_jobs - 1 (status[3] is the cursor).
-__global__ __launch_bounds__(64) void k_draft_align_long(const unsigned char* __restrict__ bps, const DraftJob* __restrict__ jobs, int jb_base, int n_jobs, int band_tol,
-                                                         unsigned* __restrict__ ents, int* __restrict__ dtab, unsigned* __restrict__ tags, int* __restrict__ n_tags,
-                                                         int* __restrict__ status) {
-    const int lane = threadIdx.x;
-    while (true) {
-        int jb = 0;
-        if (lane == 0) jb = atomicAdd(status + 3, 1);
-        jb = __builtin_amdgcn_readfirstlane(jb);
-        if (jb >= n_jobs) break;
-        jb += jb_base;
-        const DraftJob J = jobs[jb];
-        const int q_len = J.q.len, t_len = J.t.len, max_d = J.max_d;
-        int* __restrict__ DT = dtab + J.dtab_off;
-        int* V = DT + 2 * (max_d + 1);                                      // [2 * max_d + 2] each
-        int* U = V + (2 * max_d + 2);
-        unsigned* Wq = reinterpret_cast<unsigned*>(U + (2 * max_d + 2));
-        unsigned* Wt = Wq + draft_words(q_len);
-        for (int i = lane; i < 2 * (2 * max_d + 2); i += 64) V[i] = 0;
-        for (int i = lane; i < draft_words(q_len); i += 64) Wq[i] = draft_window(bps, J.q, 16 * i);
-        for (int i = lane; i < draft_words(t_len); i += 64) Wt[i] = draft_window(bps, J.t, 16 * i);
-        __syncthreads();
-        const int k_off = max_d, band_size = band_tol * 2;
-        unsigned* __restrict__ E = ents + J.ent_off;
-        unsigned* __restrict__ TG = tags + J.tag_off;
-        int best_m = -1, min_k = 0, max_k = 0;
-        long long n_ent = 0;
-        int fin_d = -1, fin_k = 0;
-        bool overflow = false;
-        for (int d = 0; d < max_d; d++) {
-            if (max_k - min_k > band_size) break;
-            const int nk = (max_k - min_k) / 2 + 1;
-            if (n_ent + nk > J.ent_cap) { overflow = true; break; }
-            if (lane == 0) { DT[2 * d] = (int)n_ent; DT[2 * d + 1] = min_k; }
-            int my_best = -1;
-            unsigned long long done_any = 0ull;
-            int done_at = 0;
-            for (int it = 0; it * 64 < nk && !done_any; it++) {
-                const int idx = it * 64 + lane;
-                const bool on = idx < nk;
-                const int k = min_k + 2 * idx;
-                int x = 0, y = 0;
-                bool fin = false;
-                if (on) {
-                    unsigned pre_minus;
-                    if (k == min_k || (k != max_k && V[k - 1 + k_off] < V[k + 1 + k_off])) { pre_minus = 0u; x = V[k + 1 + k_off]; }
-                    else { pre_minus = 1u; x = V[k - 1 + k_off] + 1; }
-                    y = x - k;
-                    const int x1 = x;
-                    while (true) {
-                        const int rem = min(q_len - x, t_len - y);
-                        if (rem <= 0) break;
-                        const unsigned df = draft_lds_window(Wq, x) ^ draft_lds_window(Wt, y);
-                        const int m = min(df ? (int)(__clz(df) >> 1) : 16, rem);
-                        x += m; y += m;
-                        if (m < 16) break;
-                    }
-                    E[2 * (n_ent + idx)] = (unsigned)x1;
-                    E[2 * (n_ent + idx) + 1] = (pre_minus << 31) | (unsigned)x;
-                    fin = x >= q_len || y >= t_len;
-                }
-                __syncthreads();            // (orders the reads of V above before the writes below; the fence makes them visible across lanes)
-                if (on) { V[k + k_off] = x; U[k + k_off] = x + y; my_best = max(my_best, x + y); }
-                done_any = __ballot(on && fin);
-                if (done_any) done_at = it * 64 + (int)__builtin_ctzll(done_any);
-                __syncthreads();
-            }
-            if (done_any) {
-                fin_d = d; fin_k = min_k + 2 * done_at;
-                n_ent += done_at + 1;
-                break;
-            }
-            n_ent += nk;
-            best_m = max(best_m, wave_max(my_best));
-            int lo = max_k, hi = min_k;
-            for (int c = 0; c * 64 < nk; c++) {
-                const int idx = c * 64 + lane;
-                const bool ok = idx < nk && U[min_k + 2 * idx + k_off] >= best_m - band_tol;
-                const unsigned long long Bm = __ballot(ok);
-                if (Bm) {
-                    lo = min(lo, min_k + 2 * (c * 64 + (int)__builtin_ctzll(Bm)));
-                    hi = max(hi, min_k + 2 * (c * 64 + 63 - (int)__builtin_clzll(Bm)));
-                }
-            }
-            max_k = hi + 1; min_k = lo - 1;
-            __syncthreads();
-        }
-        if (overflow && lane == 0) atomicOr(status, DRAFT_ST_CAP);
-        if (lane == 0) TG[0] = draft_tag(0, 0, 3);
-        long long n_col = 1;
-        if (fin_d >= 0 && !overflow) {
-            int* path = V;                  // V / U are no longer needed: the record index of every d on the path
-            __syncthreads();
-            if (lane == 0) {
-                int ck = fin_k;
-                for (int cd = fin_d; cd >= 0; cd--) {
-                    const int at = DT[2 * cd] + (ck - DT[2 * cd + 1]) / 2;
-                    path[cd] = at;
-                    ck = (E[2ll * at + 1] >> 31) ? ck - 1 : ck + 1;
-                }
-            }
-            __syncthreads();
-            int jj = 0, py = 0, px = 0;
-            bool bad_delta = false;
-            const long long col_cap = (long long)q_len + t_len + 2;
-            for (int cd = 0; cd <= fin_d; cd++) {
-                const long long at = path[cd];
-                const int x1 = (int)E[2 * at], x2 = (int)(E[2 * at + 1] & 0x7fffffffu);
-                if (cd > 0) {
-                    const bool x_step = E[2 * at + 1] >> 31;
-                    if (n_col + 1 > col_cap) { overflow = true; break; }
-                    if (x_step) {
-                        jj += 1;
-                        if (jj >= 255) bad_delta = true;
-                        if (lane == 0) TG[n_col] = draft_tag(py, jj & 255, draft_lds_base(Wq, px));
-                        px += 1;
-                    } else {
-                        jj = 0;
-                        py += 1;
-                        if (lane == 0) TG[n_col] = draft_tag(py, 0, 4);
-                    }
-                    n_col += 1;
-                }
-                const int run = x2 - x1;
-                if (run > 0) {
-                    if (n_col + run > col_cap) { overflow = true; break; }
-                    for (int t = lane; t < run; t += 64) TG[n_col + t] = draft_tag(py + 1 + t, 0, draft_lds_base(Wq, px + t));
-                    n_col += run; px += run; py += run; jj = 0;
-                }
-            }
-            if (lane == 0 && bad_delta) atomicOr(status, DRAFT_ST_DELTA);
-            if (lane == 0 && overflow) atomicOr(status, DRAFT_ST_CAP);
-        }
-        if (lane == 0) n_tags[jb] = (int)n_col;
+        if (cap_hit && lane == 0) atomicOr(status + DRAFT_SLOT_FLAGS, DRAFT_ST_CAP);
+        if (lane == 0) out_len[ld] = draft_cns_emit(L, C, TB, out + L.out_off, g_col, g_ck, g_t, cap_hit, min_cov, status);
         __syncthreads();
     }
 }
@@ -495,7 +436,7 @@ __global__ __launch_bounds__(64) void k_draft_align_long(const unsigned char* __
 // counted yet names the next link, one pass over the chunks from its chunk on counts (and clears) the members with that link.
 // So a link's number is the lowest member index that carries it, as update_col numbers them (falcon.c tag loop), the counts are
 // the sums over the chunks, and the strict `score > best` breaks ties as k_draft_cns does.  Everything else - scores, S2 / S2F,
-// the best-predecessor table, the trace-back with its link-index quirk - is k_draft_cns'.
+// the best-predecessor table, the trace-back with its link-index quirk (draft_cns_emit) - is k_draft_cns'.
 struct DraftMember { long long p, end; unsigned prev; int pad; };
 
 __global__ __launch_bounds__(64) void k_draft_cns_deep(const DraftJob* __restrict__ jobs, const DraftLadder* __restrict__ ladders, int n_ladders, const unsigned* __restrict__ tags,
@@ -508,7 +449,7 @@ __global__ __launch_bounds__(64) void k_draft_cns_deep(const DraftJob* __restric
     const int lane = threadIdx.x;
     while (true) {
         int ld = 0;
-        if (lane == 0) ld = atomicAdd(status + 4, 1);
+        if (lane == 0) ld = atomicAdd(status + DRAFT_SLOT_CNS_DEEP, 1);
         ld = __builtin_amdgcn_readfirstlane(ld);
         if (ld >= n_ladders) break;
         const DraftLadder L = ladders[ld];
@@ -589,7 +530,7 @@ __global__ __launch_bounds__(64) void k_draft_cns_deep(const DraftJob* __restric
                         ck++;
                     }
                     if (lane == 0) {
-                        if (delta < DRAFT_S2_LDS) S2[t & 1][delta][kk] = best; else S2F[((t & 1) * 256 + delta) * 5 + kk] = best;
+                        draft_s2_put(S2, S2F, t, delta, kk, best);
                         C[slot * 5 + kk] = best_p;
                     }
                     if (best > g_best) { g_best = best; g_col = (unsigned)(slot * 5 + kk); g_ck = best_ck; g_t = t; }
@@ -599,31 +540,8 @@ __global__ __launch_bounds__(64) void k_draft_cns_deep(const DraftJob* __restric
             }
             if (cap_hit) break;
         }
-        if (cap_hit && lane == 0) atomicOr(status, DRAFT_ST_CAP);
-        // ---- the sequence, back to front (falcon.c:440-478), then turned around: k_draft_cns' trace-back ------------------------
-        int len = 0;
-        if (lane == 0) {
-            char* __restrict__ o = out + L.out_off;
-            if (g_col != DRAFT_NONE && !cap_hit) {
-                char bb = '$';
-                int ck = g_ck, i = g_t;
-                unsigned col = g_col;
-                while (true) {
-                    if (ck >= 0 && ck < 5) bb = (unsigned)TB[2 * i + 1] > min_cov ? "ACGT-"[ck] : "acgt-"[ck];
-                    const unsigned bp = C[col];
-                    if (bp == DRAFT_NONE || len >= 2 * L.t_len) break;
-                    i = (int)(bp >> 11);
-                    const int j = (int)((bp >> 3) & 255u);
-                    ck = (int)(bp & 7u);
-                    col = (unsigned)((TB[2 * i] + j) * 5 + ck);
-                    if (bb != '-') o[len++] = bb;
-                }
-                for (int a = 0, b = len - 1; a < b; a++, b--) { const char c = o[a]; o[a] = o[b]; o[b] = c; }
-            } else if (!cap_hit) {
-                atomicOr(status, DRAFT_ST_BASE);
-            }
-            out_len[ld] = len;
-        }
+        if (cap_hit && lane == 0) atomicOr(status + DRAFT_SLOT_FLAGS, DRAFT_ST_CAP);
+        if (lane == 0) out_len[ld] = draft_cns_emit(L, C, TB, out + L.out_off, g_col, g_ck, g_t, cap_hit, min_cov, status);
         __syncthreads();
     }
 }
