@@ -168,6 +168,7 @@ EXTRA_SYMBOLS = [
     ("hinge_debug_force_exact", C.c_int, [_VP, C.c_int]),
     ("hinge_debug_force_general_mask", C.c_int, [_VP, C.c_int]),
     ("hinge_debug_fallback_reads", C.c_int, [_VP, _VP]),
+    ("hinge_debug_long_reads", C.c_int, [_VP, _VP]),
     ("hinge_debug_heavy_items", C.c_int, [_VP, _VP]),
     ("hinge_debug_pileup_order", C.c_int, [_VP, C.c_int32, _VP, _VP]),
 ]
@@ -305,6 +306,20 @@ class Context:
         self._ck(self.lib.hinge_debug_fallback_reads(self.h, _ptr(out)))
         return int(out[0])
 
+    def long_reads(self) -> int:
+        """Reads the last mask/annotate pass ran through the long-read tier: those of the part whose coverage profile has more
+        than 5120 bins (~204 kb at reso 40) and therefore lives in device memory instead of LDS (0: the tier was not launched)."""
+        out = np.zeros(2, np.int64)
+        self._ck(self.lib.hinge_debug_long_reads(self.h, _ptr(out)))
+        return int(out[0])
+
+    def long_reads_final(self) -> int:
+        """Of long_reads(), the reads the long-read tier ran again with the exact MIN_COV in a one-sweep pass: the long reads on the
+        guard-band list, or all of them if the prediction missed the band (0 for a two-sweep pass)."""
+        out = np.zeros(2, np.int64)
+        self._ck(self.lib.hinge_debug_long_reads(self.h, _ptr(out)))
+        return int(out[1])
+
     def heavy_items(self):
         """(half-size, full-size): undecided annotations of the last hinge pass by the k_hinge_call instance that took them."""
         out = np.zeros(2, np.int64)
@@ -350,6 +365,11 @@ class Context:
         return int(v.value)
 
     def filter_mask_annotate(self, p: FilterParams):
+        """Masks and annotations of the part's reads (exact MIN_COV: after filter_stats + filter_median).  Reads of any length
+        below 2^30 bases (HINGE_E_CAPACITY beyond: an annotation packs position and type into 31 bits): profiles of more than
+        5120 bins (~204 kb at reso 40) are built in device memory by the long-read tier, one more launch, only for parts that
+        have such a read (HINGE_E_DEVICE if that memory cannot be had).  HINGE_E_RANGE: an overlap coordinate beyond
+        rlen + cut_off.  The same holds for filter_sweep, filter_run and the _async / batch calls."""
         self._ck(self.lib.hinge_filter_mask_annotate(self.h, C.byref(p)))
 
     def filter_hinges(self, p: FilterParams):
@@ -393,6 +413,8 @@ class Context:
         return off, pos[:tot], typ[:tot], ish[:tot]
 
     def coverage_bins(self, r0: int, r1: int, reso: int, cutoff: int):
+        """(nbins[r1 - r0 + 1], cov[sum(nbins)]): the cutoff-`cutoff` coverage bins of reads r0..r1, reads of any length (profiles
+        of more than 10240 bins are built in device memory)."""
         n = r1 - r0 + 1
         nb = np.zeros(n, np.int32)
         self._ck(self.lib.hinge_filter_coverage_bins(self.h, r0, r1, reso, cutoff, _ptr(nb), None, 0))

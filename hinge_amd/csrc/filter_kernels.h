@@ -897,13 +897,26 @@ __device__ __forceinline__ void run_feed(RunState& r, int base, unsigned long lo
 // PT / OT: FilterDev / AnnoOut, possibly qualified with the constant address space (k_mask_annotate_q20 passes them in device
 // memory: every field is then a scalar load at its point of use instead of an SGPR that is live - or spilled - across the read loop).
 constexpr int SPEC_DEFERRED = 1 << 30;   // mask_gate_annotate's return value: the read emitted nothing and waits for the exact MIN_COV
-template <typename PT, typename OT, typename ZF, typename CF>
+// Where mask_annotate_body keeps a read's two histograms and its candidate list.
+// LdsProfiles: the wavefront's slot of the workgroup's dynamic LDS, 2 * kcap ints; the candidates go where the cutoff profile was.
+// A read whose bins do not fit the slot (only possible when the host clamped kcap to KCAP_LDS_MAX) belongs to the long-read tier
+// (filter_long_kernels.h) and is passed over silently.
+constexpr int KCAP_LDS_MAX = 160 * 1024 / (WAVES_PER_BLOCK * 2 * (int)sizeof(int));   // 5120 bins: reads up to ~204 kb at reso 40
+struct LdsProfiles {
+    static constexpr bool LONG = false;
+    // The sync hook: called (wave-uniformly) between a phase in which some lanes write the histograms or cand[] and one in which other
+    // lanes read them.  Nothing for LDS (a wavefront's LDS accesses are ordered); DeviceProfiles (filter_long_kernels.h) fences.
+    __device__ __forceinline__ void operator()() const {}
+};
+// ST: the storage policy of the caller (its sync hook is all that is used here; cand[] is the caller's pointer).
+template <typename PT, typename OT, typename ZF, typename CF, typename ST = LdsProfiles>
 __device__ __forceinline__ int mask_gate_annotate(const PT& P, const int reso, const int MIN_COV, const int i, const int lane,
                                                    const int K0, const RunState& run, ZF z, CF c, int* cand, const OT& o,
                                                    const long long row, const int n_pile, const bool cov_done = false,
                                                    const bool cand_in_profile = true /*cand[] overwrites what z() reads*/,
                                                    const unsigned long long flag_words = ~0ull /*bit w clear: no bin of [64 w, 64 w + 63] can be an annotation*/,
-                                                   const int band = 0 /*MODE_SPEC: MIN_COV is only known to lie in [MIN_COV - band, MIN_COV + band]*/) {
+                                                   const int band = 0 /*MODE_SPEC: MIN_COV is only known to lie in [MIN_COV - band, MIN_COV + band]*/,
+                                                   const ST sync = ST()) {
     // What every read needs of the parameters and output pointers, looked up TOGETHER: where P and o are in device memory
     // (k_mask_annotate_q20) each look-up at its point of use is a scalar-load round trip of its own in the read's dependency
     // chain - six of them, one behind the other, before this.
@@ -1036,6 +1049,7 @@ __device__ __forceinline__ int mask_gate_annotate(const PT& P, const int reso, c
     }
     // merge (filter.cpp:817-829) - sequential on a short list, in place
     int m = 0;
+    sync();
     if (lane == 0) {
         int cur = cand[0];
         for (int t = 1; t < ncand; t++) {
@@ -1053,6 +1067,7 @@ __device__ __forceinline__ int mask_gate_annotate(const PT& P, const int reso, c
         cand[m++] = cur;
     }
     m = __builtin_amdgcn_readfirstlane(m);
+    sync();
     if (m > 0 && !cand_in_profile) gate_sums();
     // gate: fp32, IEEE divide, NaN compares false (filter.cpp:861-865)
     bool gate_skip = true;
@@ -1114,22 +1129,26 @@ struct SpecArgs {
     int* cov_tot;
     const int* nbins0;
 };
-template <int RESO>
+template <int RESO, typename ST = LdsProfiles>
 __device__ __forceinline__ void mask_annotate_body(const FilterDev& P, int r_begin, int r_end, const int64_t* __restrict__ row_ptr,
                                                    const int2* __restrict__ a_span, const int* __restrict__ rlen,
                                                    const int* __restrict__ d_min_cov, int kcap, const AnnoOut& o,
                                                    const int* __restrict__ read_list, const unsigned* __restrict__ list_count, const SpecArgs& sa,
-                                                   int block_index, int n_blocks) {
+                                                   int block_index, int n_blocks, const ST st = ST()) {
     extern __shared__ int lds[];
     const int lane = lane_id();
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform by construction; lets the per-read control flow go scalar
-    int* h0 = lds + (size_t)wib * 2 * kcap;
-    int* hc = h0 + kcap;
     const int wave = block_index * WAVES_PER_BLOCK + wib;
+    int *h0, *hc, *cand;
+    if constexpr (ST::LONG) { h0 = st.scratch + (size_t)wave * 3 * kcap; hc = h0 + kcap; cand = hc + kcap; }
+    else { h0 = lds + (size_t)wib * 2 * kcap; hc = h0 + kcap; cand = hc; }
     const int nwaves = n_blocks * WAVES_PER_BLOCK;
     const int MIN_COV = *d_min_cov;
     const int reso = RESO > 0 ? RESO : P.reso;   // compile-time 40 in the shipped configuration: no runtime divisions
-    if (sa.mode == MODE_FINAL && *sa.spec_state != 0) read_list = nullptr;   // the prediction missed the band: everything again
+    if (sa.mode == MODE_FINAL && *sa.spec_state != 0) {   // the prediction missed the band: everything again
+        if constexpr (ST::LONG) { read_list = st.all_list; list_count = st.all_count; }   // (of this tier's reads)
+        else read_list = nullptr;
+    }
     const int n_items = read_list ? (int)*list_count : r_end - r_begin + 1;
     const int band = sa.mode == MODE_SPEC ? sa.band : 0;
     long long blk_cov = 0, blk_slot = 0;   // MODE_SPEC: this wavefront's share of total_cov / num_slot (filter.cpp:666,672)
@@ -1142,6 +1161,8 @@ __device__ __forceinline__ void mask_annotate_body(const FilterDev& P, int r_beg
         const int2* __restrict__ row = a_span + s;
         // bins this read can touch: events are <= rlen + cut_off for well-formed input
         int kb = bin_of<RESO>(rl + max(P.cut_off, 0), reso) + 2;
+        if constexpr (ST::LONG) { if (kb + 1 <= st.kcap_lds) continue; }   // fits the LDS slot: the LDS kernel's read
+        else { if (kb + 1 > kcap) continue; }                                // the long-read tier's
         kb = min(kb, kcap);
         const int kclamp = kb - 1;
         int mx0 = INT_MIN, mxc = INT_MIN;
@@ -1169,6 +1190,7 @@ __device__ __forceinline__ void mask_annotate_body(const FilterDev& P, int r_beg
                 int4* zc = reinterpret_cast<int4*>(hc);
                 for (int t = lane; t < (kb + 3) / 4; t += WAVE) { z0[t] = make_int4(0, 0, 0, 0); zc[t] = make_int4(0, 0, 0, 0); }
                 cleared = true;
+                st();
             }
 #pragma unroll
             for (int u = 0; u < LOADS_IN_FLIGHT; u++) {
@@ -1204,6 +1226,7 @@ __device__ __forceinline__ void mask_annotate_body(const FilterDev& P, int r_beg
             if (val != 0) atomicAdd(&hh[idx], val);   // a counter is non-zero only if some event had that (valid) bin
         }
         HINGE_ABLATE_POINT(1)
+        st();
         mx0 = wave_max(mx0);
         mxc = wave_max(mxc);
         const int K0 = nbins_of<RESO>(n, mx0, reso);
@@ -1242,6 +1265,7 @@ __device__ __forceinline__ void mask_annotate_body(const FilterDev& P, int r_beg
             run_feed(run, base, __ballot(c > MIN_COV) & V, V, reso);   // c[j] > 0 after subtracting MIN_COV
             if (band > 0) near |= (__ballot(c > MIN_COV - band) ^ __ballot(c > MIN_COV + band)) & V;
         }
+        st();
         if (sa.mode == MODE_SPEC) {   // the read's mean coverage, as k_cov_stats has it (filter.cpp:642-656)
             long long t = 0;
             for (int j = lane; j < K0; j += WAVE) t += h0[j];
@@ -1260,9 +1284,9 @@ __device__ __forceinline__ void mask_annotate_body(const FilterDev& P, int r_beg
         }
         int used = 0;
         if (near == 0ull)
-            used = mask_gate_annotate(P, reso, MIN_COV, i, lane, K0, run, [&](int j) { return h0[j]; }, [&](int j) { return hc[j]; }, hc, o, (long long)s, n,
+            used = mask_gate_annotate(P, reso, MIN_COV, i, lane, K0, run, [&](int j) { return h0[j]; }, [&](int j) { return hc[j]; }, cand, o, (long long)s, n,
                                       sa.mode == MODE_FINAL /*the first sweep stored the bins*/,
-                                      false /*the candidates go where the cutoff profile was: the gate reads the plain one*/, ~0ull, band);
+                                      false /*the candidates go where the cutoff profile was: the gate reads the plain one*/, ~0ull, band, st);
         else if (o.cov_out) {   // (a deferred read still owes its coverage bins: the final launch does not store them)
             int* __restrict__ dst = o.cov_out + o.cov_off[i - o.cov_base];
             for (int j = lane; j < K0; j += WAVE) dst[j] = h0[j];
@@ -1932,16 +1956,22 @@ __global__ void k_hinge_exact(FilterDev P, const int64_t* __restrict__ row_ptr, 
 // Materialised coverage bins of one cutoff for reads r0..r1 (for .coverage.txt / debugging).
 // Two modes: count (cov == nullptr) writes nbins only; fill writes bins at out_off[i - r0].
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BLOCK) void k_coverage_bins(int r0, int r1, const int64_t* __restrict__ row_ptr, const int2* __restrict__ a_span,
-                                                         int reso, int cutoff, int kcap, int* __restrict__ nbins,
-                                                         const int64_t* __restrict__ out_off, int* __restrict__ cov, int* __restrict__ status) {
+// LONG (filter_long_kernels.h): the histogram of a wavefront is a slot of device memory, and the wavefronts take the reads of
+// `list` (those whose bins the count mode found beyond kcap_lds) instead of r0..r1.  The LDS form passes such reads over when a
+// long launch follows (kcap_lds > 0); without one, bins beyond the slot are ST_RANGE as before.
+template <bool LONG>
+__device__ __forceinline__ void coverage_bins_body(int r0, int r1, const int64_t* __restrict__ row_ptr, const int2* __restrict__ a_span,
+                                                   int reso, int cutoff, int kcap, int* __restrict__ nbins,
+                                                   const int64_t* __restrict__ out_off, int* __restrict__ cov, int* __restrict__ status,
+                                                   int kcap_lds, int* __restrict__ scratch, const int* __restrict__ list, int n_list) {
     extern __shared__ int lds[];
     const int lane = lane_id();
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform by construction; lets the per-read control flow go scalar
-    int* h = lds + (size_t)wib * kcap;
     const int wave = blockIdx.x * WAVES_PER_BLOCK + wib;
     const int nwaves = gridDim.x * WAVES_PER_BLOCK;
-    for (int i = r0 + wave; i <= r1; i += nwaves) {
+    int* h = LONG ? scratch + (size_t)wave * kcap : lds + (size_t)wib * kcap;
+    for (int it = wave; it < (LONG ? n_list : r1 - r0 + 1); it += nwaves) {
+        const int i = LONG ? list[it] : r0 + it;
         const int64_t s = row_ptr[i], e = row_ptr[i + 1];
         int mx = INT_MIN;
         for (int64_t k = s + lane; k < e; k += WAVE) {
@@ -1952,13 +1982,15 @@ __global__ __launch_bounds__(BLOCK) void k_coverage_bins(int r0, int r1, const i
         const int K = nbins_of<0>((int)(e - s), mx, reso);
         if (lane == 0) nbins[i - r0] = K;
         if (cov == nullptr) continue;
-        if (K > kcap) { if (lane == 0) atomicOr(status, ST_RANGE); continue; }
+        if (K > kcap) { if (lane == 0 && (LONG || kcap_lds == 0)) atomicOr(status, ST_RANGE); continue; }
         for (int k = lane; k < K; k += WAVE) h[k] = 0;
+        if (LONG) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
         for (int64_t k = s + lane; k < e; k += WAVE) {
             const int2 v = a_span[k];
             atomicAdd(&h[bin_of<0>(v.x + cutoff, reso)], 1);
             atomicAdd(&h[bin_of<0>(v.y - cutoff, reso)], -1);
         }
+        if (LONG) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
         int carry = 0;
         const int64_t o = out_off[i - r0];
         for (int base = 0; base < K; base += WAVE) {
@@ -1969,6 +2001,12 @@ __global__ __launch_bounds__(BLOCK) void k_coverage_bins(int r0, int r1, const i
             carry = wave_last(v);
         }
     }
+}
+__global__ __launch_bounds__(BLOCK) void k_coverage_bins(int r0, int r1, const int64_t* __restrict__ row_ptr, const int2* __restrict__ a_span,
+                                                         int reso, int cutoff, int kcap, int* __restrict__ nbins,
+                                                         const int64_t* __restrict__ out_off, int* __restrict__ cov, int* __restrict__ status,
+                                                         int kcap_lds) {
+    coverage_bins_body<false>(r0, r1, row_ptr, a_span, reso, cutoff, kcap, nbins, out_off, cov, status, kcap_lds, nullptr, nullptr, 0);
 }
 
 }  // namespace hinge

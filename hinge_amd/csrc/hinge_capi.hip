@@ -10,6 +10,7 @@
 #include <vector>
 #include "../../include/hinge_hip.h"
 #include "filter_kernels.h"
+#include "filter_long_kernels.h"
 #include "hinge_call_kernel.h"
 #include "align_kernels.h"
 #include "select_kernel.h"
@@ -91,6 +92,12 @@ struct hinge_ctx {
     bool min_cov_pending = false;   // hinge_filter_set_min_cov is applied by the next launch that needs it
     int min_cov_value = 0;
     std::vector<int> h_rlen;      // host copy of the read lengths (length buckets of K2)
+    // the long-read tier (filter_long_kernels.h): reads of the current part whose bins do not fit the general kernel's LDS slot
+    DevBuf long_list, long_scratch;   // [count | read indices] on the device; the histograms of the tier's wavefronts
+    std::vector<int> long_list_h;     // host copy of long_list (the upload is asynchronous)
+    int n_long = 0, long_kcap = 0;    // their number, bins of the longest (a multiple of 4)
+    int long_key[4] = {-1, -1, -1, -1};   // r_begin, r_end, reso, cut_off the list was made for (forgotten by hinge_set_reads)
+    int64_t long_ran = 0;             // reads the last mask / annotate pass ran through the tier (hinge_debug_long_reads)
     unsigned max_pile = 0;        // facts about the current part's pile-ups (k_pileup_facts)
     bool spans_in_range = false;
     // tests: run the general K2 kernel where the q20 kernel would be chosen
@@ -146,10 +153,10 @@ struct hinge_ctx {
 };
 
 enum KernelId { KID_STATS = 0, KID_MEDIAN, KID_MASK_ANNOTATE, KID_MASK_FALLBACK, KID_HINGE_COUNT, KID_HINGE_CALL, KID_HINGE_EXACT, KID_COVERAGE_BINS, KID_TRIM_CLASSIFY,
-                KID_PILEUP_FACTS, KID_MATCHING_POSITION, KID_SELECT_EDGES, KID_SPEC_PREDICT, KID_MASK_FINAL, KID_CNS_REALIGN, KID_CNS_COLUMNS, KID_CNS_VOTE, KID_CNS_CALL, KID_DRAFT_ALIGN, KID_DRAFT_CNS, KID_DRAFT_ALIGN_LONG, KID_DRAFT_CNS_DEEP, KID_COUNT };
+                KID_PILEUP_FACTS, KID_MATCHING_POSITION, KID_SELECT_EDGES, KID_SPEC_PREDICT, KID_MASK_FINAL, KID_CNS_REALIGN, KID_CNS_COLUMNS, KID_CNS_VOTE, KID_CNS_CALL, KID_DRAFT_ALIGN, KID_DRAFT_CNS, KID_DRAFT_ALIGN_LONG, KID_DRAFT_CNS_DEEP, KID_MASK_LONG, KID_COUNT };
 static const char* const KERNEL_NAMES[KID_COUNT] = {"k_cov_stats", "k_median_hist", "k_mask_annotate", "k_mask_annotate_fallback", "k_hinge_count", "k_hinge_call", "k_hinge_exact",
                                                      "k_coverage_bins", "k_trim_classify", "k_pileup_facts", "k_matching_position", "k_select_edges", "k_spec_predict",
-                                                     "k_mask_annotate_final", "k_cns_realign", "k_cns_columns", "k_cns_vote", "k_cns_call", "k_draft_align", "k_draft_cns", "k_draft_align_long", "k_draft_cns_deep"};
+                                                     "k_mask_annotate_final", "k_cns_realign", "k_cns_columns", "k_cns_vote", "k_cns_call", "k_draft_align", "k_draft_cns", "k_draft_align_long", "k_draft_cns_deep", "k_mask_annotate_long"};
 
 struct ProfScope {
     hinge_ctx* c;
@@ -271,6 +278,8 @@ static int check_params(hinge_ctx* ctx, const hinge_filter_params* p) {
     if (!p) return fail(ctx, HINGE_E_ARG, "params == NULL");
     if (p->reso <= 0) return fail(ctx, HINGE_E_ARG, "reso must be > 0");
     if (p->coverage_fraction == 0) return fail(ctx, HINGE_E_ARG, "coverage_frac_repeat_annotation == 0 divides by zero in the reference");
+    if (ctx && ctx->max_rlen >= (1 << 30))   // (before any launch of a pass)
+        return fail(ctx, HINGE_E_CAPACITY, "a read of 2^30 or more bases: an annotation packs its position and type into 31 bits (longest read: " + std::to_string(ctx->max_rlen) + ")");
     return HINGE_OK;
 }
 
@@ -330,7 +339,7 @@ void hinge_ctx_destroy(hinge_ctx* ctx) {
                      &ctx->cmask, &ctx->rflags, &ctx->nbins0, &ctx->anno_buf, &ctx->anno_off, &ctx->anno_cnt, &ctx->hinge_flag,
                      &ctx->work_list, &ctx->heavy_list, &ctx->fallback_list, &ctx->bucket_list, &ctx->k2_heads, &ctx->keep, &ctx->span16, &ctx->exact_queue, &ctx->arena, &ctx->scalars, &ctx->med, &ctx->wave_totals, &ctx->trace, &ctx->trace_off, &ctx->tlen,
                      &ctx->eff_reads, &ctx->pair_sel, &ctx->pair_a, &ctx->pair_out, &ctx->cov_buf, &ctx->cov_off_d, &ctx->cov_nb, &ctx->k2c,
-                     &ctx->cov_tot, &ctx->redo_list, &ctx->spec_sample, &ctx->final_batch, &ctx->heavy2_list, &ctx->rd_head, &ctx->rd_next2, &ctx->rl2, &ctx->img_row_base, &ctx->img_rec_rel, &ctx->bspan16};
+                     &ctx->cov_tot, &ctx->redo_list, &ctx->spec_sample, &ctx->final_batch, &ctx->heavy2_list, &ctx->rd_head, &ctx->rd_next2, &ctx->rl2, &ctx->img_row_base, &ctx->img_rec_rel, &ctx->bspan16, &ctx->long_list, &ctx->long_scratch};
     for (DevBuf* b : all) release(*b);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -369,6 +378,8 @@ int hinge_set_reads(hinge_ctx* ctx, int32_t n_reads, const int32_t* rlen, const 
     // the coverage-output layout (slot offsets, buffer size) was made from the OLD read lengths: forget it
     ctx->cov_key[0] = ctx->cov_key[1] = ctx->cov_key[2] = ctx->cov_key[3] = -1;
     ctx->cov_valid = false;
+    ctx->long_key[0] = ctx->long_key[1] = ctx->long_key[2] = ctx->long_key[3] = -1;   // (so was the list of the long reads)
+    ctx->n_long = 0;
     size_t n = (size_t)n_reads;
     if ((rc = ensure(ctx, ctx->mask_own, sizeof(int2) * n))) return rc;
     if ((rc = ensure(ctx, ctx->mean_own, sizeof(int) * n))) return rc;
@@ -645,6 +656,30 @@ int hinge_debug_fallback_reads(hinge_ctx* ctx, int64_t* out) {
     return HINGE_OK;
 }
 
+// tests: out[0] = reads the last mask / annotate pass ran through the long-read tier (k_mask_annotate_long) in its first sweep;
+// out[1] = of those, the reads its MODE_FINAL launch ran again: the long reads on the guard-band list, all of them if the prediction
+// missed the band, 0 for a two-sweep pass
+int hinge_debug_long_reads(hinge_ctx* ctx, int64_t* out) {
+    if (!ctx || !out) return HINGE_E_ARG;
+    out[0] = ctx->long_ran;
+    out[1] = 0;
+    if (ctx->pass_mode == 0 || ctx->long_ran == 0) return HINGE_OK;
+    CK(hipSetDevice(ctx->device));
+    CK(hipStreamSynchronize(ctx->stream));
+    unsigned n = 0;
+    int missed = 0;
+    CK(hipMemcpy(&n, &((Scalars*)ctx->scalars.p)->redo_count, sizeof(n), hipMemcpyDeviceToHost));
+    CK(hipMemcpy(&missed, &((Scalars*)ctx->scalars.p)->spec_state, sizeof(missed), hipMemcpyDeviceToHost));
+    if (missed != 0) { out[1] = ctx->long_ran; return HINGE_OK; }
+    n = std::min(n, (unsigned)ctx->n_reads);
+    std::vector<int> redo(n);
+    if (n) CK(hipMemcpy(redo.data(), ctx->redo_list.p, sizeof(int) * n, hipMemcpyDeviceToHost));
+    std::vector<int> lr(ctx->long_list_h.begin() + 1, ctx->long_list_h.end());
+    std::sort(lr.begin(), lr.end());
+    for (int i : redo) out[1] += std::binary_search(lr.begin(), lr.end(), i);
+    return HINGE_OK;
+}
+
 // tests: undecided annotations the last hinge pass sent through the half-size / the full-size instance of k_hinge_call
 int hinge_debug_heavy_items(hinge_ctx* ctx, int64_t* out) {
     if (!ctx || !out) return HINGE_E_ARG;
@@ -674,6 +709,60 @@ static int kcap_for(hinge_ctx* ctx, const hinge_filter_params* p) {
     // bins a read can touch: (rlen + cut_off) / reso + 1 (bin_of) + 2 slack, rounded to 4
     int k = (ctx->max_rlen + std::max(p->cut_off, 0)) / p->reso + 4;
     return (k + 3) & ~3;
+}
+
+// what the LDS kernels are launched with: reads beyond it are the long-read tier's
+static int kcap_lds_for(hinge_ctx* ctx, const hinge_filter_params* p) { return std::min(kcap_for(ctx, p), (int)KCAP_LDS_MAX); }
+
+// The reads of the current part whose bins exceed the LDS slot, listed once per (part, reso, cut_off).  No read of the data set
+// is that long (every input inside the old limit): nothing is looked at, nothing is launched.
+static const int LONG_WAVES_MAX = 256;   // wavefronts of a long-tier launch (also: slots spec_args_of keeps for them in wave_totals)
+// wavefronts of a long-tier launch over n reads of kcap bins each (whole workgroups), the scratch kept under 128 MiB
+static int long_waves(int n, int kcap, int arrays) {
+    const long long slot = (long long)arrays * kcap * (long long)sizeof(int);
+    const int fit = (int)std::max<long long>(WAVES_PER_BLOCK, ((128LL << 20) / slot) / WAVES_PER_BLOCK * WAVES_PER_BLOCK);
+    const int want = (n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK * WAVES_PER_BLOCK;
+    return std::max((int)WAVES_PER_BLOCK, std::min(std::min(want, fit), LONG_WAVES_MAX));
+}
+static int long_reads_prepare(hinge_ctx* ctx, const hinge_filter_params* p) {
+    if (kcap_for(ctx, p) <= KCAP_LDS_MAX) {   // (and the list, if there is one, is not for these parameters: forget its key)
+        ctx->n_long = 0;
+        ctx->long_key[0] = ctx->long_key[1] = ctx->long_key[2] = ctx->long_key[3] = -1;
+        return HINGE_OK;
+    }
+    const int key[4] = {ctx->r_begin, ctx->r_end, p->reso, p->cut_off};
+    if (memcmp(key, ctx->long_key, sizeof(key)) == 0) return HINGE_OK;
+    const int cut = std::max(p->cut_off, 0);
+    std::vector<int>& l = ctx->long_list_h;
+    l.assign(1, 0);
+    int longest = 0;
+    for (int i = ctx->r_begin; i <= ctx->r_end; i++) {
+        const int rl = ctx->h_rlen[(size_t)i];
+        if ((rl + cut) / p->reso + 4 > KCAP_LDS_MAX) { l.push_back(i); longest = std::max(longest, rl); }   // the kernels' test: kb + 1 > kcap
+    }
+    l[0] = (int)l.size() - 1;
+    ctx->n_long = l[0];
+    ctx->long_kcap = ((longest + cut) / p->reso + 4 + 3) & ~3;
+    memcpy(ctx->long_key, key, sizeof(key));
+    if (ctx->n_long == 0) return HINGE_OK;
+    int rc = ensure(ctx, ctx->long_list, sizeof(int) * l.size());
+    if (rc) return rc;
+    CK(hipMemcpyAsync(ctx->long_list.p, l.data(), sizeof(int) * l.size(), hipMemcpyHostToDevice, ctx->stream));
+    return HINGE_OK;
+}
+// the tier's scratch: a failed allocation leaves everything resident as it was (ensure() frees the buffer's old, smaller self only)
+static int long_scratch_ensure(hinge_ctx* ctx, int waves, int kcap, int arrays, int longest_bins) {
+    const size_t bytes = (size_t)waves * arrays * kcap * sizeof(int);
+    if (ctx->long_scratch.p && ctx->long_scratch.bytes >= bytes) return HINGE_OK;
+    release(ctx->long_scratch);
+    void* q = nullptr;
+    if (hipMalloc(&q, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, HINGE_E_DEVICE, "no device memory for the coverage profiles of the long reads: " + std::to_string(bytes) + " bytes for " + std::to_string(waves) +
+                                             " wavefronts, longest read " + std::to_string(ctx->max_rlen) + " bases (" + std::to_string(longest_bins) + " bins)");
+    }
+    ctx->long_scratch.p = q; ctx->long_scratch.bytes = bytes; ctx->long_scratch.owned = true;
+    return HINGE_OK;
 }
 
 // one memset clears every per-pass device scalar (totals, counters, exact queue, arena, status)
@@ -924,7 +1013,8 @@ static int spec_args_of(hinge_ctx* ctx, int mode, int grid, SpecArgs* out) {
     a.redo_list = (int*)ctx->redo_list.p; a.redo_count = &sc(ctx)->redo_count; a.redo_cap = (unsigned)ctx->n_reads;
     if (mode == MODE_SPEC) {
         ctx->n_wave_totals = grid * WAVES_PER_BLOCK;
-        int rc = ensure(ctx, ctx->wave_totals, sizeof(unsigned long long) * 2 * (size_t)ctx->n_wave_totals);
+        // (+ the slots of a long-tier launch behind this one: growing the buffer then would lose what this launch wrote)
+        int rc = ensure(ctx, ctx->wave_totals, sizeof(unsigned long long) * 2 * ((size_t)ctx->n_wave_totals + LONG_WAVES_MAX));
         if (rc) return rc;
     }
     a.wave_totals = (unsigned long long*)ctx->wave_totals.p;
@@ -1126,9 +1216,8 @@ static int k2_fallback(hinge_ctx* ctx, const hinge_filter_params* p, int mode, i
     SpecArgs sa;
     int rc = spec_args_of(ctx, mode, std::min(grid, 64), &sa);
     if (rc) return rc;
-    const int kcap = kcap_for(ctx, p);
+    const int kcap = kcap_lds_for(ctx, p);   // (longer reads on the list: passed over, the long-read tier's)
     const size_t lds = (size_t)WAVES_PER_BLOCK * 2 * kcap * sizeof(int);
-    if (lds > 160 * 1024) return fail(ctx, HINGE_E_RANGE, "read too long for the LDS histogram (max ~200 kb)");
     if (lds > 48 * 1024 && lds > ctx->lds_attr_set) {
         CK(hipFuncSetAttribute((const void*)k_mask_annotate<40>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         CK(hipFuncSetAttribute((const void*)k_mask_annotate<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1140,16 +1229,60 @@ static int k2_fallback(hinge_ctx* ctx, const hinge_filter_params* p, int mode, i
     return HINGE_OK;
 }
 
-static int launch_mask_annotate(hinge_ctx* ctx, const hinge_filter_params* p, int mode = MODE_CLASSIC) {
+// The long-read tier behind the LDS kernels of a sweep (any mode): the part's long reads, one per wavefront, their profiles in
+// device memory (k_mask_annotate_long).  MODE_CLASSIC / MODE_SPEC: the host's list, the same reads the LDS kernels passed over
+// whether they met them in [r_begin, r_end] or among the fast kernel's hand-backs; MODE_SPEC sums go where the general kernel's
+// go (cov_tot behind the fast kernel, else mean_cov and wave_totals slots of the tier's own behind the general kernel's).
+// MODE_FINAL: the long reads of the guard-band list, or all of them if the prediction missed the band.
+static int launch_long_tier(hinge_ctx* ctx, const hinge_filter_params* p, int mode) {
+    int rc = long_reads_prepare(ctx, p);
+    if (rc) return rc;
+    if (mode != MODE_FINAL) ctx->long_ran = ctx->n_long;
+    if (ctx->n_long == 0) return HINGE_OK;
+    const int kcap = ctx->long_kcap;
+    const int waves = long_waves(ctx->n_long, kcap, 3), grid = waves / WAVES_PER_BLOCK;
+    if ((rc = long_scratch_ensure(ctx, waves, kcap, 3, kcap))) return rc;
+    SpecArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.mode = mode; sa.band = ctx->spec_band;
+    sa.mean_cov = ctx->mean_cov;
+    sa.spec_state = &sc(ctx)->spec_state;
+    sa.redo_list = (int*)ctx->redo_list.p; sa.redo_count = &sc(ctx)->redo_count; sa.redo_cap = (unsigned)ctx->n_reads;
+    if (mode == MODE_SPEC) {
+        // (the general kernel ran in front - on the whole part or on the fast kernel's hand-backs, which every long read is - and
+        // spec_args_of kept LONG_WAVES_MAX slots behind its own)
+        const size_t need = sizeof(unsigned long long) * 2 * ((size_t)ctx->n_wave_totals + waves);
+        if (!ctx->wave_totals.p || ctx->wave_totals.bytes < need) return fail(ctx, HINGE_E_CAPACITY, "long-read tier: no room behind the general kernel's wave totals");
+        sa.wave_totals = (unsigned long long*)ctx->wave_totals.p + 2 * (size_t)ctx->n_wave_totals;
+        ctx->n_wave_totals += waves;
+        if (ctx->pass_mode == 1) { sa.cov_tot = (int*)ctx->cov_tot.p; sa.nbins0 = (const int*)ctx->nbins0.p; }
+    }
+    DeviceProfiles st;
+    st.scratch = (int*)ctx->long_scratch.p; st.kcap_lds = KCAP_LDS_MAX;
+    st.all_list = (const int*)ctx->long_list.p + 1; st.all_count = (const unsigned*)ctx->long_list.p;
+    const int* list = mode == MODE_FINAL ? (const int*)ctx->redo_list.p : st.all_list;
+    const unsigned* count = mode == MODE_FINAL ? (const unsigned*)&sc(ctx)->redo_count : st.all_count;
+    const int* min_cov = mode == MODE_SPEC ? &sc(ctx)->spec_min_cov : &sc(ctx)->min_cov;
+    ProfScope _ps(ctx, KID_MASK_LONG);
+#define LAUNCH_MASK_LONG(RESO)                                                                                                       \
+    hipLaunchKernelGGL(k_mask_annotate_long<RESO>, dim3(grid), dim3(BLOCK), 0, ctx->stream, to_dev(p), ctx->r_begin, ctx->r_end,      \
+                       (const int64_t*)ctx->row_ptr.p, (const int2*)ctx->a_span.p, (const int*)ctx->rlen.p, min_cov, kcap,            \
+                       anno_out(ctx), list, count, sa, st)
+    if (p->reso == 40) LAUNCH_MASK_LONG(40); else LAUNCH_MASK_LONG(0);
+#undef LAUNCH_MASK_LONG
+    CK(hipGetLastError());
+    return HINGE_OK;
+}
+
+static int launch_mask_annotate_lds(hinge_ctx* ctx, const hinge_filter_params* p, int mode) {
     {
         int rc = flush_min_cov(ctx);
         if (rc) return rc;
         if ((rc = prepare_cov_out(ctx, p))) return rc;
     }
     if (mode == MODE_SPEC) ctx->n_wave_totals = 0;   // (set again below if the general kernel takes part in the sweep)
-    const int kcap = kcap_for(ctx, p);
+    const int kcap = kcap_lds_for(ctx, p);
     const size_t lds = (size_t)WAVES_PER_BLOCK * 2 * kcap * sizeof(int);
-    if (lds > 160 * 1024) return fail(ctx, HINGE_E_RANGE, "read too long for the LDS histogram (max ~200 kb)");
     if (lds > 48 * 1024 && lds > ctx->lds_attr_set) {
         CK(hipFuncSetAttribute((const void*)k_mask_annotate<40>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         CK(hipFuncSetAttribute((const void*)k_mask_annotate<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1193,6 +1326,12 @@ static int launch_mask_annotate(hinge_ctx* ctx, const hinge_filter_params* p, in
     else LAUNCH_MASK_ANNOTATE(0, grid, (const int*)nullptr, (const unsigned*)nullptr, sa);
     CK(hipGetLastError());
     return HINGE_OK;
+}
+
+static int launch_mask_annotate(hinge_ctx* ctx, const hinge_filter_params* p, int mode = MODE_CLASSIC) {
+    int rc = launch_mask_annotate_lds(ctx, p, mode);
+    if (rc) return rc;
+    return launch_long_tier(ctx, p, mode);
 }
 
 // The mask / annotation sweep over n resident parts (contexts on one device and one stream): ONE k_mask_annotate_q20_batch launch
@@ -1270,6 +1409,7 @@ static int launch_mask_annotate_parts(hinge_ctx** ctxs, int n, const hinge_filte
         hinge_ctx* c = ctxs[k];
         const int nr = c->r_end - c->r_begin + 1;
         if ((rc = k2_fallback(c, p, mode, std::max(1, std::min((nr + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 1 << 20))))) return rc;
+        if ((rc = launch_long_tier(c, p, mode))) return rc;
     }
     return HINGE_OK;
 }
@@ -1582,13 +1722,15 @@ int hinge_filter_coverage_bins(hinge_ctx* ctx, int32_t r0, int32_t r1, int32_t r
     CK(hipSetDevice(ctx->device));
     const size_t n = (size_t)(r1 - r0 + 1);
     struct Tmp {   // freed on every return path
-        int* nb = nullptr; int64_t* off = nullptr; int* cov = nullptr;
-        ~Tmp() { if (nb) (void)hipFree(nb); if (off) (void)hipFree(off); if (cov) (void)hipFree(cov); }
+        int* nb = nullptr; int64_t* off = nullptr; int* cov = nullptr; int* lst = nullptr;
+        ~Tmp() { if (nb) (void)hipFree(nb); if (off) (void)hipFree(off); if (cov) (void)hipFree(cov); if (lst) (void)hipFree(lst); }
     } d;
     CK(hipMalloc(&d.nb, sizeof(int) * n));
-    const int kcap = ((ctx->max_rlen + std::max(cutoff, 0)) / reso + 4 + 3) & ~3;
+    // one histogram per wavefront: 10240 bins of LDS at most, reads with more go through k_coverage_bins_long afterwards
+    const int kcap_all = ((ctx->max_rlen + std::max(cutoff, 0)) / reso + 4 + 3) & ~3;
+    const int kcap = std::min(kcap_all, 2 * (int)KCAP_LDS_MAX);
+    const int long_follows = kcap_all > kcap ? kcap : 0;
     const size_t lds = (size_t)WAVES_PER_BLOCK * kcap * sizeof(int);
-    if (lds > 160 * 1024) return fail(ctx, HINGE_E_RANGE, "coverage_bins: read too long for the LDS histogram");
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_coverage_bins, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const int grid = grid_for_reads(ctx, (int)n, WAVES_PER_BLOCK);
     // its own status word: the pass status (capacity / median flags of an asynchronous pass) is not this function's to clear
@@ -1597,7 +1739,7 @@ int hinge_filter_coverage_bins(hinge_ctx* ctx, int32_t r0, int32_t r1, int32_t r
     {
         ProfScope _ps(ctx, KID_COVERAGE_BINS);
         hipLaunchKernelGGL(k_coverage_bins, dim3(grid), dim3(BLOCK), lds, ctx->stream, r0, r1, (const int64_t*)ctx->row_ptr.p,
-                           (const int2*)ctx->a_span.p, reso, cutoff, kcap, d.nb, (const int64_t*)nullptr, (int*)nullptr, st);
+                           (const int2*)ctx->a_span.p, reso, cutoff, kcap, d.nb, (const int64_t*)nullptr, (int*)nullptr, st, long_follows);
     }
     CK(hipGetLastError());
     CK(hipMemcpyAsync(nbins, d.nb, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -1613,14 +1755,31 @@ int hinge_filter_coverage_bins(hinge_ctx* ctx, int32_t r0, int32_t r1, int32_t r
     {
         ProfScope _ps(ctx, KID_COVERAGE_BINS);
         hipLaunchKernelGGL(k_coverage_bins, dim3(grid), dim3(BLOCK), lds, ctx->stream, r0, r1, (const int64_t*)ctx->row_ptr.p,
-                           (const int2*)ctx->a_span.p, reso, cutoff, kcap, d.nb, (const int64_t*)d.off, d.cov, st);
+                           (const int2*)ctx->a_span.p, reso, cutoff, kcap, d.nb, (const int64_t*)d.off, d.cov, st, long_follows);
     }
     CK(hipGetLastError());
+    if (long_follows) {
+        std::vector<int> lst;
+        for (size_t i = 0; i < n; i++) if (nbins[i] > kcap) lst.push_back(r0 + (int)i);
+        if (!lst.empty()) {
+            const int waves = long_waves((int)lst.size(), kcap_all, 1);
+            int rc = long_scratch_ensure(ctx, waves, kcap_all, 1, kcap_all);
+            if (rc) return rc;
+            CK(hipMalloc(&d.lst, sizeof(int) * lst.size()));
+            CK(hipMemcpyAsync(d.lst, lst.data(), sizeof(int) * lst.size(), hipMemcpyHostToDevice, ctx->stream));
+            ProfScope _ps(ctx, KID_COVERAGE_BINS);
+            hipLaunchKernelGGL(k_coverage_bins_long, dim3(waves / WAVES_PER_BLOCK), dim3(BLOCK), 0, ctx->stream, r0, r1, (const int64_t*)ctx->row_ptr.p,
+                               (const int2*)ctx->a_span.p, reso, cutoff, kcap_all, d.nb, (const int64_t*)d.off, d.cov, st, (int*)ctx->long_scratch.p,
+                               (const int*)d.lst, (int)lst.size());
+            CK(hipGetLastError());
+            CK(hipStreamSynchronize(ctx->stream));   // (lst lives on this frame)
+        }
+    }
     CK(hipMemcpyAsync(cov, d.cov, sizeof(int) * (size_t)off[n], hipMemcpyDeviceToHost, ctx->stream));
     int stv = 0;
     CK(hipMemcpyAsync(&stv, st, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
-    if (stv & ST_RANGE) return fail(ctx, HINGE_E_RANGE, "coverage_bins: bins exceed LDS capacity");
+    if (stv & ST_RANGE) return fail(ctx, HINGE_E_RANGE, "coverage_bins: overlap coordinate beyond read length + cutoff");
     return HINGE_OK;
 }
 
@@ -1798,7 +1957,7 @@ int hinge_filter_finish_batch_async(hinge_ctx** ctxs, int32_t n, const hinge_fil
             hinge_ctx* c = ctxs[k0 + k];
             if ((rc = flush_min_cov(c))) return rc;
             if ((rc = prepare_cov_out(c, p))) return rc;
-            kcap = std::max(kcap, kcap_for(c, p));
+            kcap = std::max(kcap, kcap_lds_for(c, p));
             nr_max = std::max(nr_max, c->r_end - c->r_begin + 1);
             MaskFinalPart& a = B.part[k];
             a.r_begin = c->r_begin; a.r_end = c->r_end;
@@ -1809,7 +1968,6 @@ int hinge_filter_finish_batch_async(hinge_ctx** ctxs, int32_t n, const hinge_fil
             if ((rc = spec_args_of(c, MODE_FINAL, 0, &a.sa))) return rc;
         }
         const size_t lds = (size_t)WAVES_PER_BLOCK * 2 * kcap * sizeof(int);
-        if (lds > 160 * 1024) return fail(ctx, HINGE_E_RANGE, "read too long for the LDS histogram (max ~200 kb)");
         if (lds > 48 * 1024 && lds > ctx->lds_attr_final) {
             CK(hipFuncSetAttribute((const void*)k_mask_final_batch<40>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             CK(hipFuncSetAttribute((const void*)k_mask_final_batch<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1827,6 +1985,10 @@ int hinge_filter_finish_batch_async(hinge_ctx** ctxs, int32_t n, const hinge_fil
         if (p->reso == 40) hipLaunchKernelGGL(k_mask_final_batch<40>, dim3(gper * nb), dim3(BLOCK), lds, ctx->stream, to_dev(p), (const MaskFinalBatch*)ctx->final_batch.p, kcap);
         else hipLaunchKernelGGL(k_mask_final_batch<0>, dim3(gper * nb), dim3(BLOCK), lds, ctx->stream, to_dev(p), (const MaskFinalBatch*)ctx->final_batch.p, kcap);
         CK(hipGetLastError());
+        _ps.stop();
+        // (the long reads of a guard-band list were passed over: their own tier, part by part - no launch for a part without any)
+        for (int k = 0; k < nb; k++)
+            if ((rc = launch_long_tier(ctxs[k0 + k], p, MODE_FINAL))) return rc;
     }
     return HINGE_OK;
 }

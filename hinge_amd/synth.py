@@ -538,6 +538,12 @@ CONFIGS = {
     # reads from 4 kb to 120 kb: every LDS-slot class of the mask/annotate kernel (1, 2, 4 slots, and > 91 kb: general kernel)
     "long_reads": SynthSpec(genome_len=400_000, coverage=40, len_dist="lognormal", len_mean=25000, len_sigma=0.7, len_min=4000,
                             len_max=120000, repeat_len=(9000, 9000), repeat_copies=(3, 3), seed=31, trace_jitter=15),
+    # reads up to 1.3 Mb (ultra-long nanopore): 40 of the 1 067 reads have more coverage bins than the mask/annotate kernel's LDS slot
+    # holds (> 204 kb: the long-read tier, profiles in device memory), 2 more than a whole workgroup's LDS would; long repeats put
+    # annotations (35) and hinges (32) on them.  (At coverage 25: 1 667 reads, 66 / 3 such, a 107 MB .las; the suite keeps 16 for time.)
+    "ultra_long": SynthSpec(genome_len=4_000_000, coverage=16, len_dist="lognormal", len_mean=60000, len_sigma=1.0, len_min=5000,
+                            len_max=1_300_000, repeat_len=(150000, 400000), repeat_copies=(2, 3), n_repeat_families=4, seed=61,
+                            trace_jitter=15),
     # trace spacing 200: two bytes per trace value on disk (tspace > 125), a QV track at that spacing
     "tspace200": SynthSpec(genome_len=150_000, coverage=45, seed=41, tspace=200, with_qv=True, n_repeat_families=2,
                            repeat_len=(6000, 6000), repeat_copies=(2, 2), trace_jitter=28),

@@ -33,7 +33,7 @@ extern "C" {
 #define HINGE_E_CAPACITY (-3)  /* an internal device buffer overflowed even after regrowing    */
 #define HINGE_E_UNDEFINED (-4) /* input on which the reference itself is undefined (e.g. no
                                   read >= 5000 bp in a part: filter.cpp:660-666)               */
-#define HINGE_E_RANGE (-5)     /* coordinate outside the read (bin beyond the LDS histogram)   */
+#define HINGE_E_RANGE (-5)     /* coordinate outside the read (beyond read length + cut_off)   */
 
 typedef struct hinge_ctx hinge_ctx;
 
@@ -152,7 +152,16 @@ int hinge_set_read_restriction(hinge_ctx* ctx, const uint8_t* keep);
 int hinge_filter_set_min_cov(hinge_ctx* ctx, int32_t min_cov);
 int hinge_filter_get_min_cov(hinge_ctx* ctx, int32_t* min_cov);
 /* K2: coverage mask (filter.cpp:696-789) + repeat annotation and merge (filter.cpp:796-829) + the
- * fp32 end-coverage gate (filter.cpp:842-865) for reads r_begin..r_end; writes their mask rows.  */
+ * fp32 end-coverage gate (filter.cpp:842-865) for reads r_begin..r_end; writes their mask rows.
+ * Reads of any length below 2^30 bases: a read's coverage profile lives in LDS while it has at most 5120 bins
+ * ((rlen + cut_off) / reso + 4: ~204 kb at the shipped reso 40); longer reads of the part take k_mask_annotate_long behind the
+ * LDS kernels, one more launch, profiles in device memory (12 bytes per bin of the longest such read and wavefront of that
+ * launch, at most 256 wavefronts and 128 MiB; a part without such a read launches what it always did).  This holds for every
+ * call that runs K2: hinge_filter_run, the staged / _async / _batch_async calls and hinge_filter_sweep.
+ *   HINGE_E_CAPACITY: a read of 2^30 or more bases (an annotation packs position << 1 | type into an int).
+ *   HINGE_E_DEVICE: the profiles' device memory could not be allocated (the message names the read length); what is
+ *   resident stays as it was.
+ *   HINGE_E_RANGE keeps its meaning: an overlap coordinate beyond rlen + cut_off, on a read of any length.              */
 int hinge_filter_mask_annotate(hinge_ctx* ctx, const hinge_filter_params* p);
 /* K3: hinge calling (filter.cpp:867-1068) for the reads that passed the gate; reads the whole mask
  * table (masks of B reads).                                                                       */
@@ -198,7 +207,8 @@ int hinge_filter_get_masks(hinge_ctx* ctx, int32_t* mask, int32_t* cmask, uint8_
  * Call with pos == NULL to get only `off` (to size the arrays).                                   */
 int hinge_filter_get_annotations(hinge_ctx* ctx, int64_t* off, int32_t* pos, int32_t* type, uint8_t* is_hinge);
 /* Cutoff-`cutoff` coverage bins (the .coverage.txt payload, filter.cpp:599-602) for reads
- * r0..r1 inclusive: nbins[r1-r0+1]; if cov != NULL, bins of read i start at sum(nbins[<i]).      */
+ * r0..r1 inclusive: nbins[r1-r0+1]; if cov != NULL, bins of read i start at sum(nbins[<i]).
+ * Reads of any length: profiles of more than 10240 bins are built in device memory (k_coverage_bins_long). */
 int hinge_filter_coverage_bins(hinge_ctx* ctx, int32_t r0, int32_t r1, int32_t reso, int32_t cutoff, int32_t* nbins,
                                int32_t* cov, int64_t cov_cap);
 /* .coverage.txt without a second sweep: with coverage_out(1), K2 (hinge_filter_mask_annotate*) also stores the cutoff-0 coverage
@@ -417,6 +427,10 @@ int hinge_debug_force_exact(hinge_ctx* ctx, int mode);
 int hinge_debug_force_general_mask(hinge_ctx* ctx, int on);
 /* out[0] = reads the last K2 pass handed from the fast kernel to the general one. */
 int hinge_debug_fallback_reads(hinge_ctx* ctx, int64_t* out);
+/* out[0] = reads the last mask / annotate pass (the first sweep of a one-sweep pass) ran through the long-read tier; out[1] = of
+ * those, the reads the pass's MODE_FINAL launch of the tier ran again (the long reads of the guard-band list; all of them if the
+ * prediction missed the band; 0 for a two-sweep pass).  Synchronises. */
+int hinge_debug_long_reads(hinge_ctx* ctx, int64_t* out);
 /* out[0..1] = undecided annotations the last hinge pass put through the half-size / full-size k_hinge_call. */
 int hinge_debug_heavy_items(hinge_ctx* ctx, int64_t* out);
 /* pos_out[k] = position of element k after std::sort(compare_overlap) of n keys, through the wavefront-parallel replay. */
