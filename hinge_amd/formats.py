@@ -426,3 +426,54 @@ def write_paf(path: str, rlen: np.ndarray, aread, bread, comp, ab, ae, bb, be, g
             f.write(("%s\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t255\n" % (
                 read_name(a, int(rlen[a])), int(rlen[a]), s0, e0, "-" if c else "+", read_name(b, int(rlen[b])), int(rlen[b]), s1, e1,
                 ml, max(e0 - s0, e1 - s1))).encode())
+
+
+# --------------------------------------------------------------------------------------
+# `hinge fasta2db FASTA DB`  (python3 -m hinge_amd.formats)
+# --------------------------------------------------------------------------------------
+
+def read_fasta_bases(path: str) -> List[np.ndarray]:
+    """Every record of a FASTA file as uint8 0..3 (A C G T, either case; any other letter becomes A, as DAZZ_DB's fasta2DB
+    stores it).  Sequence lines are joined, blanks inside them dropped; a record without bases is kept (length 0)."""
+    lut = np.zeros(256, np.uint8)
+    for ch, v in (("a", 0), ("c", 1), ("g", 2), ("t", 3)):
+        lut[ord(ch)] = lut[ord(ch.upper())] = v
+    out: List[np.ndarray] = []
+    cur: Optional[List[bytes]] = None
+    with open(path, "rb") as f:
+        for line in f:
+            if line.startswith(b">"):
+                if cur is not None:
+                    out.append(lut[np.frombuffer(b"".join(cur), np.uint8)])
+                cur = []
+            elif cur is not None:
+                cur.append(b"".join(line.split()))
+    if cur is not None:
+        out.append(lut[np.frombuffer(b"".join(cur), np.uint8)])
+    return out
+
+
+def fasta2db(fasta: str, db_name: str) -> int:
+    """Write DB (NAME.db, .NAME.idx, .NAME.bps) with the records of a FASTA file as its reads, nothing trimmed.  Returns the count."""
+    bases = read_fasta_bases(fasta)
+    write_db(db_name, np.asarray([len(b) for b in bases], np.int32), bases=bases)
+    return len(bases)
+
+
+def _main(argv) -> int:
+    import sys
+    if len(argv) != 2:
+        sys.stderr.write("usage: hinge fasta2db <fasta> <db>\n")
+        return 1
+    try:
+        n = fasta2db(argv[0], argv[1])
+    except OSError as e:
+        sys.stderr.write("fasta2db: %s\n" % e)
+        return 1
+    print("fasta2db: %d reads -> %s" % (n, db_paths(argv[1])[0]))
+    return 0
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(_main(sys.argv[1:]))
