@@ -113,6 +113,8 @@ SYMBOLS = [
     ("hinge_consensus_get_indels", C.c_int, [_VP, C.c_int64, _VP, C.c_int64, C.POINTER(C.c_int64)]),
     ("hinge_draft_mappings", C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int32, _VP, _VP]),
     ("hinge_draft_ladders", C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP]),
+    ("hinge_trace_run", C.c_int, [_VP, C.c_int64, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), _VP, _VP]),
+    ("hinge_trace_last_stats", C.c_int, [_VP, _VP]),
     ("hinge_profile_report", C.c_int, [_VP, _VP, _VP]),
     ("hinge_timer_start", C.c_int, [_VP]),
     ("hinge_timer_stop_ms", C.c_int, [_VP, C.POINTER(C.c_float)]),
@@ -509,6 +511,31 @@ class Context:
 
     def check(self):
         self._ck(self.lib.hinge_filter_check(self.h))
+
+    def trace_run(self, placements, tspace: int = 100, band: int = 0, band_max: int = 0):
+        """hinge_trace_run (`hinge paf2las`): trace points for placements = rows of (aread, bread, comp, abpos, aepos, bbpos, bepos)
+        on the two DBs given through Consensus(ctx, draft_db, read_db).  band / band_max 0 = the defaults (HINGE_TRACE_BAND[_MAX],
+        128 / 1024).  Returns (alns: CNS_ALN_DTYPE rows with tlen / trace_off filled, trace uint16, diffs int32, status int32 [n, 2]
+        = (final status, final W); status 0 = a record) and leaves stats() of the call in trace_stats()."""
+        pl = np.asarray(placements, dtype=np.int64).reshape(-1, 7)
+        n = pl.shape[0]
+        a = np.zeros(max(n, 1), dtype=CNS_ALN_DTYPE)
+        for k, name in enumerate(("aread", "bread", "comp", "abpos", "aepos", "bbpos", "bepos")):
+            a[name][:n] = pl[:, k]
+        out = np.zeros(max(n, 1), dtype=CNS_ALN_DTYPE)
+        cap = int(sum(2 * ((int(r[4]) - 1) // tspace - int(r[3]) // tspace + 1) for r in pl if r[4] > r[3] >= 0)) if tspace > 0 else 0
+        trace = np.zeros(max(cap, 1), dtype=np.uint16)
+        diffs = np.zeros(max(n, 1), dtype=np.int32)
+        status = np.zeros((max(n, 1), 2), dtype=np.int32)
+        nt = C.c_int64(0)
+        self._ck(self.lib.hinge_trace_run(self.h, n, _ptr(a), int(tspace), int(band), int(band_max), _ptr(out), _ptr(trace), cap, C.byref(nt), _ptr(diffs), _ptr(status)))
+        return out[:n], trace[:nt.value], diffs[:n], status[:n]
+
+    def trace_stats(self) -> dict:
+        """Of the last trace_run: batches, largest direction scratch of a batch (bytes), placement runs, rounds, widened, dropped."""
+        st = np.zeros(8, np.int64)
+        self._ck(self.lib.hinge_trace_last_stats(self.h, _ptr(st)))
+        return dict(zip(("batches", "scratch_bytes", "runs", "rounds", "widened", "dropped"), [int(v) for v in st[:6]]))
 
     def profile_enable(self, max_launches: int):
         self._ck(self.lib.hinge_profile_enable(self.h, int(max_launches)))

@@ -414,17 +414,19 @@ def write_fasta(path: str, rlen: np.ndarray, seed: int = 0, line: int = 80, gz: 
                 f.write(seq[k:k + line] + b"\n")
 
 
-def write_paf(path: str, rlen: np.ndarray, aread, bread, comp, ab, ae, bb, be, gz: bool = False) -> None:
-    """One 12-column PAF line per overlap; target coordinates on the forward strand of B (minimap convention)."""
+def write_paf(path: str, rlen: np.ndarray, aread, bread, comp, ab, ae, bb, be, gz: bool = False, rlen_b=None) -> None:
+    """One 12-column PAF line per overlap; target coordinates on the forward strand of B (minimap convention).  rlen_b: the
+    lengths of the target sequences where they are not the queries' (`hinge paf2las`: query = read, target = contig)."""
     import gzip
     rlen = np.asarray(rlen)
+    rlen_b = rlen if rlen_b is None else np.asarray(rlen_b)
     op = gzip.open if gz else open
     with op(path, "wb") as f:
         for a, b, c, s0, e0, s1, e1 in zip(np.asarray(aread).tolist(), np.asarray(bread).tolist(), np.asarray(comp).tolist(),
                                            np.asarray(ab).tolist(), np.asarray(ae).tolist(), np.asarray(bb).tolist(), np.asarray(be).tolist()):
             ml = min(e0 - s0, e1 - s1)
             f.write(("%s\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t255\n" % (
-                read_name(a, int(rlen[a])), int(rlen[a]), s0, e0, "-" if c else "+", read_name(b, int(rlen[b])), int(rlen[b]), s1, e1,
+                read_name(a, int(rlen[a])), int(rlen[a]), s0, e0, "-" if c else "+", read_name(b, int(rlen_b[b])), int(rlen_b[b]), s1, e1,
                 ml, max(e0 - s0, e1 - s1))).encode())
 
 
@@ -460,8 +462,53 @@ def fasta2db(fasta: str, db_name: str) -> int:
     return len(bases)
 
 
+# --------------------------------------------------------------------------------------
+# `hinge correct-head IN.fasta OUT.fasta MAP.txt`  (python3 -m hinge_amd.formats --correct-head)
+# --------------------------------------------------------------------------------------
+
+def correct_head(fasta: str, out: str, lookup: str, line: int = 60) -> Tuple[int, int]:
+    """scripts/correct_head.py of the reference without pbcore: record i (0-based, counted over ALL records) gets the header
+    m000_000/<i + 1>/0_<length>, which is what makes the "1-based id between the first two '/'" rule find it; records under 30
+    bases are dropped.  MAP.txt: old header, tab, new header or `Deleted`, one line per record.  Sequence lines of `line` letters
+    (pbcore's FastaWriter wraps at 60).  Returns (records kept, records dropped)."""
+    recs: List[Tuple[str, List[str]]] = []
+    with open(fasta, "r") as f:
+        for ln in f:
+            ln = ln.rstrip("\r\n")
+            if ln.startswith(">"):
+                recs.append((ln[1:], []))
+            elif recs and ln:
+                recs[-1][1].append(ln.strip())
+    kept = dropped = 0
+    with open(out, "w") as fo, open(lookup, "w") as fm:
+        for i, (old, parts) in enumerate(recs):
+            seq = "".join(parts)
+            if len(seq) < 30:
+                fm.write("%s\tDeleted\n" % old)
+                dropped += 1
+                continue
+            new = "m000_000/%d/0_%d" % (i + 1, len(seq))
+            fm.write("%s\t%s\n" % (old, new))
+            fo.write(">%s\n" % new)
+            for k in range(0, len(seq), line):
+                fo.write(seq[k:k + line] + "\n")
+            kept += 1
+    return kept, dropped
+
+
 def _main(argv) -> int:
     import sys
+    if argv and argv[0] == "--correct-head":
+        if len(argv) != 4:
+            sys.stderr.write("usage: hinge correct-head <in.fasta> <out.fasta> <map.txt>\n")
+            return 1
+        try:
+            kept, dropped = correct_head(argv[1], argv[2], argv[3])
+        except OSError as e:
+            sys.stderr.write("correct-head: %s\n" % e)
+            return 1
+        print("correct-head: %d records kept, %d deleted" % (kept, dropped))
+        return 0
     if len(argv) != 2:
         sys.stderr.write("usage: hinge fasta2db <fasta> <db>\n")
         return 1

@@ -405,6 +405,36 @@ typedef struct hinge_draft_rung { int32_t read, strand, start, end; } hinge_draf
 int hinge_draft_ladders(hinge_ctx* ctx, int64_t n_ladders, const int64_t* rung_off, const hinge_draft_rung* rungs, const int32_t* template_rung, int32_t band_tolerance,
                         const int64_t* out_off, char* out, int32_t* out_len);
 
+/* ---- hinge paf2las ------------------------------------------------------------------------------------------
+ * Trace points for placements whose end points are given (PAF lines: contig, read, strand, four end points).  Replaces, for
+ * such placements, the trace output of DALIGNER's Local_Alignment as LAInterface::recoverAlignment consumes it
+ * (lib/LAInterface.cpp:4125-4244; the record: include/align.h:98-110): per tspace block of A the pair (edit operations, B
+ * bases).  NOT replaced: finding the placements (seeding, chaining), local extension or trimming of the end points.
+ * Uses the two DBs given by hinge_consensus_set_db (0 = draft, 1 = reads).
+ *   placements[n]    aread, bread, comp, abpos, aepos, bbpos, bepos as in hinge_cns_alignment (B in the complemented frame when
+ *                    comp); tlen and trace_off are ignored
+ *   band, band_max   half-width W of the first round and the largest one; 0 = HINGE_TRACE_BAND / HINGE_TRACE_BAND_MAX, else
+ *                    128 / 1024.  Multiples of 8 in [8, 2048].  The alignment is the banded GLOBAL edit distance (substitution,
+ *                    insertion, deletion 1 each) over the 2 W diagonals around the straight line between the end points: optimal
+ *                    inside the band only.  A placement whose path touches the band's first or last diagonal, or whose
+ *                    |blen - alen| exceeds W, runs again at 2 W, while 2 W stays within band_max (four rounds with the defaults).
+ *   out_alns[n]      the placements in the order given with tlen and trace_off filled (tlen = 0: no record)
+ *   trace            16-bit values, trace_cap of them: must hold two per trace-point segment of EVERY placement
+ *                    (HINGE_E_CAPACITY otherwise, before any launch); *n_trace = values written
+ *   diffs[n]         the sum of a placement's segment diffs (0 without record)
+ *   status[2 n]      per placement: final status, final W.  0 OK; without record: 1 TOUCHED (still on the band's edge at the last
+ *                    W), 2 NO_PATH (|blen - alen| beyond the last W), 3 WIDE (a segment's diffs or B advance beyond a trace value:
+ *                    255 at tspace <= 125), 4 STEPS (internal: the walk did not arrive).  A placement without record never fails
+ *                    the call.
+ * HINGE_E_RANGE (before any launch) for ids or coordinates outside the reads and for abpos >= aepos or bbpos >= bepos;
+ * HINGE_E_DEVICE for a failed scratch allocation or an output slot no kernel wrote.  The direction scratch (alen x 2 W x 2 bits
+ * per placement) is allocated per batch under HINGE_TRACE_SCRATCH_MB (default 4096; HINGE_TRACE_SCRATCH_BYTES for tests).    */
+int hinge_trace_run(hinge_ctx* ctx, int64_t n, const hinge_cns_alignment* placements, int32_t tspace, int32_t band, int32_t band_max, hinge_cns_alignment* out_alns,
+                    uint16_t* trace, int64_t trace_cap, int64_t* n_trace, int32_t* diffs, int32_t* status);
+/* Of the last hinge_trace_run: out[0] batches launched, [1] largest direction scratch of a batch in bytes, [2] placement runs
+ * (a widened placement counts once per round), [3] rounds, [4] records made at a W beyond the first, [5] placements without record. */
+int hinge_trace_last_stats(hinge_ctx* ctx, int64_t* out);
+
 /* Per-kernel timing with HIP events recorded around every launch on the context's stream.
  * enable(max_launches > 0) starts a fresh recording; report() synchronises and returns total ms and
  * launch count per kernel id in [0, hinge_profile_kernels()).  select() restricts the events to the
