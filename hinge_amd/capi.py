@@ -114,6 +114,7 @@ SYMBOLS = [
     ("hinge_draft_mappings", C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int32, _VP, _VP]),
     ("hinge_draft_ladders", C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP]),
     ("hinge_trace_run", C.c_int, [_VP, C.c_int64, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), _VP, _VP]),
+    ("hinge_trace_refine", C.c_int, [_VP, C.c_int64, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), _VP, _VP, _VP]),
     ("hinge_trace_last_stats", C.c_int, [_VP, _VP]),
     ("hinge_profile_report", C.c_int, [_VP, _VP, _VP]),
     ("hinge_timer_start", C.c_int, [_VP]),
@@ -531,11 +532,37 @@ class Context:
         self._ck(self.lib.hinge_trace_run(self.h, n, _ptr(a), int(tspace), int(band), int(band_max), _ptr(out), _ptr(trace), cap, C.byref(nt), _ptr(diffs), _ptr(status)))
         return out[:n], trace[:nt.value], diffs[:n], status[:n]
 
+    def trace_refine(self, placements, tspace: int = 100, band: int = 0, band_max: int = 0, extend: int = -1, match: int = 0, diff: int = 0, min_score: int = 0):
+        """hinge_trace_refine (`hinge paf2las --ends refine`): trace_run for placements whose end points are approximate.  Every box
+        is widened by up to `extend` bases per side, and of the path the best-scoring stretch is kept (+match per equal pair, -diff
+        per edit operation; below max(1, min_score): status 5 EMPTY, no record).  extend -1, match / diff / min_score 0 = the
+        defaults (HINGE_TRACE_EXTEND / _MATCH / _DIFF / _MIN_SCORE, else 50, 1, 2, 1).  Returns (alns with the REFINED abpos / aepos /
+        bbpos / bepos where there is a record, trace, diffs, status [n, 2], score int32)."""
+        pl = np.asarray(placements, dtype=np.int64).reshape(-1, 7)
+        n = pl.shape[0]
+        a = np.zeros(max(n, 1), dtype=CNS_ALN_DTYPE)
+        for k, name in enumerate(("aread", "bread", "comp", "abpos", "aepos", "bbpos", "bepos")):
+            a[name][:n] = pl[:, k]
+        out = np.zeros(max(n, 1), dtype=CNS_ALN_DTYPE)
+        ext = int(os.environ.get("HINGE_TRACE_EXTEND") or 50) if extend == -1 else max(int(extend), 0)
+        # room for the widened boxes: no box is wider than the given one with `ext` bases on either side (the front clamped at 0)
+        cap = int(sum(2 * ((int(r[4]) + ext - 1) // tspace - max(int(r[3]) - ext, 0) // tspace + 1) for r in pl if r[4] > r[3] >= 0)) if tspace > 0 else 0
+        trace = np.zeros(max(cap, 1), dtype=np.uint16)
+        diffs = np.zeros(max(n, 1), dtype=np.int32)
+        score = np.zeros(max(n, 1), dtype=np.int32)
+        status = np.zeros((max(n, 1), 2), dtype=np.int32)
+        nt = C.c_int64(0)
+        ends = np.asarray([extend, match, diff, min_score], dtype=np.int32)
+        self._ck(self.lib.hinge_trace_refine(self.h, n, _ptr(a), int(tspace), int(band), int(band_max), _ptr(ends), _ptr(out), _ptr(trace), cap, C.byref(nt), _ptr(diffs),
+                                             _ptr(status), _ptr(score)))
+        return out[:n], trace[:nt.value], diffs[:n], status[:n], score[:n]
+
     def trace_stats(self) -> dict:
-        """Of the last trace_run: batches, largest direction scratch of a batch (bytes), placement runs, rounds, widened, dropped."""
+        """Of the last trace_run / trace_refine: batches, largest direction scratch of a batch (bytes), placement runs, rounds, widened,
+        dropped (placements without record) and, of those, the EMPTY ones of trace_refine."""
         st = np.zeros(8, np.int64)
         self._ck(self.lib.hinge_trace_last_stats(self.h, _ptr(st)))
-        return dict(zip(("batches", "scratch_bytes", "runs", "rounds", "widened", "dropped"), [int(v) for v in st[:6]]))
+        return dict(zip(("batches", "scratch_bytes", "runs", "rounds", "widened", "dropped", "empty"), [int(v) for v in st[:7]]))
 
     def profile_enable(self, max_launches: int):
         self._ck(self.lib.hinge_profile_enable(self.h, int(max_launches)))

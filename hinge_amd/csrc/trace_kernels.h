@@ -6,6 +6,7 @@
 //   k_trace_fill   one WAVEFRONT (= one 64-thread workgroup) per placement: banded global edit distance in anti-diagonal order,
 //                  the two previous anti-diagonals in LDS rings, one 2-bit direction per cell to device scratch
 //   k_trace_walk   one LANE per placement: the path back from the end cell, (edit operations, B bases) per tspace block of A
+//   k_trace_clip   in the walk's place when the end points are approximate (hinge_trace_refine): the best-scoring stretch of the path
 //
 // The band.  Cell (i, j) = i bases of A and j bases of B consumed, 0 <= i <= alen, 0 <= j <= blen.  Row i's centre diagonal is
 //   c(i) = floor((2 i (blen - alen) + alen) / (2 alen))            [= round(i (blen - alen) / alen), halves up]
@@ -30,7 +31,8 @@ constexpr int TRACE_ST_TOUCHED = 1;   // the path used a cell on the first or th
 constexpr int TRACE_ST_NO_PATH = 2;   // |blen - alen| > W, or the end cell was not reached inside the band
 constexpr int TRACE_ST_WIDE = 3;      // a segment's diffs or B advance exceeds what a trace value holds
 constexpr int TRACE_ST_STEPS = 4;     // the walk did not arrive at (0, 0) in alen + blen + 1 steps, or its diffs are not the fill's cost
-constexpr int TRACE_ST_POISON = -1;   // what the status slots hold before a launch
+constexpr int TRACE_ST_EMPTY = 5;     // k_trace_clip only: no run of the path's columns sums to max(1, min_score)
+constexpr int TRACE_ST_POISON = -1;  // what the status slots hold before a launch
 constexpr unsigned short TRACE_POISON16 = 0xffffu;   // ... and the trace slots
 constexpr int TRACE_INF = 0x3fffffff;
 constexpr int TRACE_BAND_MIN = 8, TRACE_BAND_LIMIT = 2048;   // W: a multiple of 8 in this range (16 cells per direction word; the LDS rings)
@@ -225,6 +227,99 @@ __global__ __launch_bounds__(64) void k_trace_walk(const TraceJob* __restrict__ 
     if (i != 0 || j != 0 || seg != 0 || total != cost) bad = true;
     diffs[x] = total;
     status[x] = bad ? TRACE_ST_STEPS : touched ? TRACE_ST_TOUCHED : wide ? TRACE_ST_WIDE : TRACE_ST_OK;
+}
+
+// Refined end points (hinge_trace_refine): the walk's place when the job's box is the given one widened.  One LANE per placement.
+// The path from (alen, blen) back to (0, 0) is a list of columns, one per step; a column lies on the cell it ends in (where its
+// direction is stored) and scores +match on direction 0, -diff on 1, 2 and 3.  Kept: the contiguous run of columns with the
+// largest sum; among equal sums the run that starts latest, among those the one that ends latest.
+//   walk 1   q = the sum of the columns behind the cell the walk stands on, qmin = the smallest q so far with its cell (replaced
+//            on q < qmin: of equal minima the first met, i.e. the latest end), best = the largest q - qmin with both cells
+//            (replaced on >: of equal sums the first met, i.e. the latest start).  The run begins and ends with a match column:
+//            a -diff column at either end would leave a larger sum without it.
+//   walk 2   from the kept end cell (its c and r were saved with it) to the kept start cell: k_trace_walk's body; the segment
+//            slots are those of the job's (widened) layout, so the kept segments are slots first .. first + n - 1 of it.
+// touched: only cells of kept columns count.  clip[4 x ..] = i0, j0, i1, j1 (cells of the job's box), score[x] = the sum.
+// Both loops: at most alen + blen + 1 trips, fixed before they start; nothing read that another wavefront writes.
+__global__ __launch_bounds__(64) void k_trace_clip(const TraceJob* __restrict__ jobs, int n_jobs, int W, int tspace, int tmax, int match, int diff, int min_score,
+                                                   const unsigned* __restrict__ dirs, const int* __restrict__ end_cost, unsigned short* __restrict__ trace, int* __restrict__ diffs,
+                                                   int* __restrict__ status, int* __restrict__ clip, int* __restrict__ score) {
+    const int x = blockIdx.x * 64 + threadIdx.x;
+    if (x >= n_jobs) return;
+    const TraceJob J = jobs[x];
+    const int alen = J.ae - J.ab, blen = J.be - J.bb;
+    const int cost = end_cost[x];
+    int i0 = 0, j0 = 0, i1 = 0, j1 = 0, best = 0;
+    auto done = [&](int code, int d) {
+        clip[4ll * x] = i0; clip[4ll * x + 1] = j0; clip[4ll * x + 2] = i1; clip[4ll * x + 3] = j1;
+        score[x] = best;
+        diffs[x] = d;
+        status[x] = code;
+    };
+    if (alen <= 0 || blen <= 0 || abs(blen - alen) > W || cost >= TRACE_INF || cost < 0) { done(TRACE_ST_NO_PATH, 0); return; }
+    TraceStep S;
+    S.init(alen, blen);
+    const int wpr = trace_row_words(W);
+    const unsigned* __restrict__ my_dirs = dirs + J.dir_off;
+    const int max_steps = alen + blen + 1;
+    bool bad = false;
+    // ---- walk 1: the kept run ----------------------------------------------------------------------------------------------------
+    int i = alen, j = blen, c = blen - alen;
+    long long r = alen;
+    int q = 0, qmin = 0, mi = alen, mj = blen, mc = c, c1 = c, total = 0;
+    long long mr = r, r1 = r;
+    for (int step = 0; step < max_steps; step++) {
+        if (i == 0 && j == 0) break;
+        const int k = j - i - c + W;
+        unsigned dir = 2u;
+        if (i > 0) {
+            if ((unsigned)k >= (unsigned)(2 * W)) { bad = true; break; }
+            dir = (my_dirs[(long long)(i - 1) * wpr + (k >> 4)] >> (2 * (k & 15))) & 3u;
+        }
+        if (dir != 1u && j == 0) { bad = true; break; }
+        if (dir == 0u) { i--; j--; q += match; S.back(c, r); }
+        else if (dir == 3u) { i--; j--; q -= diff; total++; S.back(c, r); }
+        else if (dir == 1u) { i--; q -= diff; total++; S.back(c, r); }
+        else { j--; q -= diff; total++; }
+        if (q - qmin > best) { best = q - qmin; i0 = i; j0 = j; i1 = mi; j1 = mj; c1 = mc; r1 = mr; }
+        if (q < qmin) { qmin = q; mi = i; mj = j; mc = c; mr = r; }
+    }
+    if (i != 0 || j != 0 || total != cost) bad = true;
+    if (bad) { done(TRACE_ST_STEPS, 0); return; }
+    if (best < max(1, min_score)) { done(TRACE_ST_EMPTY, 0); return; }
+    // ---- walk 2: the kept run's segments -----------------------------------------------------------------------------------------
+    unsigned short* __restrict__ my_trace = trace + J.trace_off;
+    const int seg_base = J.ab / tspace;
+    const int seg_first = (J.ab + i0) / tspace - seg_base;
+    i = i1; j = j1; c = c1; r = r1;
+    int seg = (J.ab + i1 - 1) / tspace - seg_base, sd = 0, sb = 0, kept = 0, cols = 0;
+    bool touched = false, wide = false;
+    auto emit = [&]() {
+        if (seg >= seg_first && seg < J.nseg) {
+            my_trace[2 * seg] = (unsigned short)min(sd, tmax);
+            my_trace[2 * seg + 1] = (unsigned short)min(sb, tmax);
+        } else bad = true;
+        if (sd > tmax || sb > tmax) wide = true;
+        kept += sd;
+    };
+    for (int step = 0; step < max_steps; step++) {
+        if (i == i0 && j == j0) break;
+        if (i <= i0 || j < j0) { bad = true; break; }               // (every kept column has an A base in front of it)
+        const int k = j - i - c + W;
+        if ((unsigned)k >= (unsigned)(2 * W)) { bad = true; break; }
+        if (k == 0 || k == 2 * W - 1) touched = true;
+        const unsigned dir = (my_dirs[(long long)(i - 1) * wpr + (k >> 4)] >> (2 * (k & 15))) & 3u;
+        const int s = (J.ab + i - 1) / tspace - seg_base;
+        if (s != seg) { emit(); seg = s; sd = 0; sb = 0; }
+        cols++;
+        if (dir == 0u) { i--; j--; sb++; S.back(c, r); }
+        else if (dir == 3u) { i--; j--; sb++; sd++; S.back(c, r); }
+        else if (dir == 1u) { i--; sd++; S.back(c, r); }
+        else { j--; sb++; sd++; }
+    }
+    emit();
+    if (i != i0 || j != j0 || seg != seg_first || match * (cols - kept) - diff * kept != best) bad = true;
+    done(bad ? TRACE_ST_STEPS : touched ? TRACE_ST_TOUCHED : wide ? TRACE_ST_WIDE : TRACE_ST_OK, kept);
 }
 
 }  // namespace hinge

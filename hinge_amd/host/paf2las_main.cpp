@@ -1,9 +1,13 @@
-// paf2las  ==  `hinge paf2las DRAFT_DB READ_DB PAF OUT.las [--band W] [--band-max W] [--tspace T] [--draft-names FASTA] [--read-names FASTA]`
+// paf2las  ==  `hinge paf2las DRAFT_DB READ_DB PAF OUT.las [--band W] [--band-max W] [--tspace T] [--draft-names FASTA] [--read-names FASTA]
+//                                [--ends given|refine] [--extend E] [--scores M,X] [--min-score S]`
 // Not a program of the reference: it stands where demo/ecoli_demo/run.sh:30-37 runs HPC.daligner + LAmerge on (draft, reads) to get
 // the draft-vs-reads .las WITH trace points that `hinge consensus` needs.  Input: placements as PAF, query = read, target =
 // contig (what `minimap2 draft.fasta reads.fasta` prints).  The base-level alignment between the given end points and its trace
 // points are computed behind the C ABI (hinge_trace_run, include/hinge_hip.h) on the GPU; this file reads the DBs and the PAF,
 // resolves names, and writes the .las (align.h:98-110: the records `Read_Overlap` reads).
+// --ends given (the default): the PAF's end points are exact (hinge_trace_run).  --ends refine: they are approximate - every
+// placement is widened by up to E bases per side and the best-scoring stretch of its path is kept (hinge_trace_refine); the
+// records carry the refined end points.
 #include "host_common.h"
 
 #include <map>
@@ -12,7 +16,8 @@
 using namespace hh;
 
 static void usage() {
-    fprintf(stderr, "usage: paf2las <draft db> <read db> <paf> <out.las> [--band W] [--band-max W] [--tspace T] [--draft-names FASTA] [--read-names FASTA]\n");
+    fprintf(stderr, "usage: paf2las <draft db> <read db> <paf> <out.las> [--band W] [--band-max W] [--tspace T] [--draft-names FASTA] [--read-names FASTA]\n"
+                    "               [--ends given|refine] [--extend E] [--scores M,X] [--min-score S]\n");
 }
 
 // first word of every header of a FASTA file -> record index
@@ -46,7 +51,9 @@ static int id_between_slashes(const std::string& name) {
 int main(int argc, char* argv[]) {
     std::vector<std::string> pos;
     int band = 0, band_max = 0, tspace = 100;
-    std::string draft_names, read_names;
+    std::string draft_names, read_names, ends_mode = "given";
+    hinge_trace_ends ends = {-1, 0, 0, 0};          // the library's defaults (50; 1, 2; 1)
+    bool ends_opts = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto val = [&](const char* name) -> const char* {
@@ -58,10 +65,21 @@ int main(int argc, char* argv[]) {
         else if (a == "--tspace") tspace = atoi(val("--tspace"));
         else if (a == "--draft-names") draft_names = val("--draft-names");
         else if (a == "--read-names") read_names = val("--read-names");
+        else if (a == "--ends") ends_mode = val("--ends");
+        else if (a == "--extend") { ends.extend = atoi(val("--extend")); ends_opts = true; if (ends.extend < 0) { usage(); return 1; } }
+        else if (a == "--scores") {
+            int m = 0, x = 0;
+            if (sscanf(val("--scores"), "%d,%d", &m, &x) != 2 || m < 1 || x < 1) { fprintf(stderr, "paf2las: --scores needs M,X (each 1..15)\n"); usage(); return 1; }
+            ends.match = m; ends.diff = x; ends_opts = true;
+        }
+        else if (a == "--min-score") { ends.min_score = atoi(val("--min-score")); ends_opts = true; if (ends.min_score < 1) { usage(); return 1; } }
         else if (a.size() > 2 && a[0] == '-' && a[1] == '-') { fprintf(stderr, "paf2las: unknown option %s\n", a.c_str()); usage(); return 1; }
         else pos.push_back(a);
     }
     if (pos.size() != 4 || tspace <= 0 || tspace > 32767 || band < 0 || band_max < 0) { usage(); return 1; }
+    if (ends_mode != "given" && ends_mode != "refine") { fprintf(stderr, "paf2las: --ends takes given or refine\n"); usage(); return 1; }
+    const bool refine = ends_mode == "refine";
+    if (ends_opts && !refine) { fprintf(stderr, "paf2las: --extend, --scores and --min-score belong to --ends refine\n"); usage(); return 1; }
     PhaseTimer tm("paf2las");
     CtxInit gpu;
     gpu.start();
@@ -134,12 +152,21 @@ int main(int argc, char* argv[]) {
     tm.mark("H2D bases");
     const int64_t n = (int64_t)pl.size();
     int64_t cap = 0;
-    for (const hinge_cns_alignment& r : pl) cap += 2 * (int64_t)((r.aepos - 1) / tspace - r.abpos / tspace + 1);
+    int room = 0;                                   // refine: no widened box reaches further than this beyond the given one
+    if (refine) {
+        const char* g = getenv("HINGE_TRACE_EXTEND");
+        room = ends.extend >= 0 ? ends.extend : (g && *g) ? std::max(atoi(g), 0) : 50;
+    }
+    for (const hinge_cns_alignment& r : pl) cap += 2 * (int64_t)((r.aepos + room - 1) / tspace - std::max(r.abpos - room, 0) / tspace + 1);
     std::vector<hinge_cns_alignment> out((size_t)std::max<int64_t>(n, 1));
     std::vector<uint16_t> trace((size_t)std::max<int64_t>(cap, 1));
     std::vector<int32_t> diffs((size_t)std::max<int64_t>(n, 1)), status((size_t)std::max<int64_t>(2 * n, 2));
     int64_t n_trace = 0;
-    if (hinge_trace_run(ctx, n, pl.data(), tspace, band, band_max, out.data(), trace.data(), cap, &n_trace, diffs.data(), status.data()) != HINGE_OK) die("trace");
+    if (refine) {
+        std::vector<int32_t> score((size_t)std::max<int64_t>(n, 1));
+        if (hinge_trace_refine(ctx, n, pl.data(), tspace, band, band_max, &ends, out.data(), trace.data(), cap, &n_trace, diffs.data(), status.data(), score.data()) != HINGE_OK)
+            die("trace");
+    } else if (hinge_trace_run(ctx, n, pl.data(), tspace, band, band_max, out.data(), trace.data(), cap, &n_trace, diffs.data(), status.data()) != HINGE_OK) die("trace");
     tm.mark("align + trace");
 
     // ---- the .las: records sorted by (aread, bread, abpos) - the placements' order ------------------------------------------------
@@ -152,7 +179,16 @@ int main(int argc, char* argv[]) {
     fwrite(&ts32, 4, 1, fo);
     const int tbytes = tspace <= 125 ? 1 : 2;
     std::vector<uint8_t> tb;
-    for (int64_t x = 0; x < n; x++) {
+    std::vector<int64_t> order((size_t)n);
+    for (int64_t x = 0; x < n; x++) order[(size_t)x] = x;
+    if (refine)                          // refined abpos: two placements of one read on one contig may have changed places
+        std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) {
+            const hinge_cns_alignment &p = out[(size_t)x], &q = out[(size_t)y];
+            if (p.aread != q.aread) return p.aread < q.aread;
+            if (p.bread != q.bread) return p.bread < q.bread;
+            return p.abpos < q.abpos;
+        });
+    for (int64_t x : order) {
         if (status[(size_t)(2 * x)] != 0) continue;
         const hinge_cns_alignment& r = out[(size_t)x];
         uint8_t rec[40];
@@ -172,7 +208,7 @@ int main(int argc, char* argv[]) {
 
     // ---- the summary line ------------------------------------------------------------------------------------------------------------
     std::map<int, int64_t> widened;      // final W -> records made there (beyond the first W)
-    int64_t dropped[5] = {0, 0, 0, 0, 0};
+    int64_t dropped[6] = {0, 0, 0, 0, 0, 0};
     int first_w = 0;
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     (void)hinge_trace_last_stats(ctx, stats);
@@ -183,20 +219,32 @@ int main(int argc, char* argv[]) {
     for (int64_t x = 0; x < n; x++) {
         const int st = status[(size_t)(2 * x)], w = status[(size_t)(2 * x + 1)];
         if (st == 0) { if (w != first_w) widened[w]++; }
-        else if (st >= 1 && st <= 4) dropped[st]++;
+        else if (st >= 1 && st <= 5) dropped[st]++;
+    }
+    std::string rtxt;                    // refine: "; clipped out N, end points moved by B bases on average" (all four of a record)
+    if (refine) {
+        long long moved = 0;
+        for (int64_t x = 0; x < n; x++)
+            if (status[(size_t)(2 * x)] == 0) {
+                const hinge_cns_alignment &o = out[(size_t)x], &g = pl[(size_t)x];
+                moved += std::abs(o.abpos - g.abpos) + std::abs(o.aepos - g.aepos) + std::abs(o.bbpos - g.bbpos) + std::abs(o.bepos - g.bepos);
+            }
+        char buf[128];
+        snprintf(buf, sizeof(buf), "; clipped out %lld, end points moved by %.1f bases on average", (long long)dropped[5], written ? (double)moved / (4.0 * (double)written) : 0.0);
+        rtxt = buf;
     }
     std::string wtxt;
     for (auto& kv : widened) wtxt += (wtxt.empty() ? "" : ", ") + std::string("W=") + std::to_string(kv.first) + ": " + std::to_string(kv.second);
-    printf("paf2las: %lld placements read, %lld written, widened %s, dropped %lld (touched %lld, no path %lld, wide %lld, steps %lld); %lld batch(es)\n", (long long)n,
+    printf("paf2las: %lld placements read, %lld written, widened %s, dropped %lld (touched %lld, no path %lld, wide %lld, steps %lld); %lld batch(es)%s\n", (long long)n,
            (long long)written, wtxt.empty() ? "0" : ("(" + wtxt + ")").c_str(), (long long)(n - written), (long long)dropped[1], (long long)dropped[2], (long long)dropped[3],
-           (long long)dropped[4], (long long)stats[0]);
+           (long long)dropped[4], (long long)stats[0], rtxt.c_str());
     for (int64_t x = 0; x < n; x++)
         if (status[(size_t)(2 * x)] != 0) {
-            static const char* const why[5] = {"", "touched the band's edge", "no path", "wide segment", "steps"};
+            static const char* const why[6] = {"", "touched the band's edge", "no path", "wide segment", "steps", "clipped out (no stretch reaches the minimum score)"};
             const hinge_cns_alignment& r = pl[(size_t)x];
             const int st = status[(size_t)(2 * x)];
             fprintf(stderr, "paf2las: dropped contig %d [%d, %d) read %d%s [%d, %d): %s at W = %d\n", r.aread, r.abpos, r.aepos, r.bread, r.comp ? " (-)" : "", r.bbpos, r.bepos,
-                    (st >= 1 && st <= 4) ? why[st] : "?", status[(size_t)(2 * x + 1)]);
+                    (st >= 1 && st <= 5) ? why[st] : "?", status[(size_t)(2 * x + 1)]);
         }
     tm.mark("write");
     return finish(ctx, tm, 0);

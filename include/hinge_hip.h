@@ -409,7 +409,8 @@ int hinge_draft_ladders(hinge_ctx* ctx, int64_t n_ladders, const int64_t* rung_o
  * Trace points for placements whose end points are given (PAF lines: contig, read, strand, four end points).  Replaces, for
  * such placements, the trace output of DALIGNER's Local_Alignment as LAInterface::recoverAlignment consumes it
  * (lib/LAInterface.cpp:4125-4244; the record: include/align.h:98-110): per tspace block of A the pair (edit operations, B
- * bases).  NOT replaced: finding the placements (seeding, chaining), local extension or trimming of the end points.
+ * bases).  NOT replaced: finding the placements (seeding, chaining).  hinge_trace_run takes the end points as exact;
+ * hinge_trace_refine below extends and clips approximate ones.
  * Uses the two DBs given by hinge_consensus_set_db (0 = draft, 1 = reads).
  *   placements[n]    aread, bread, comp, abpos, aepos, bbpos, bepos as in hinge_cns_alignment (B in the complemented frame when
  *                    comp); tlen and trace_off are ignored
@@ -431,8 +432,36 @@ int hinge_draft_ladders(hinge_ctx* ctx, int64_t n_ladders, const int64_t* rung_o
  * per placement) is allocated per batch under HINGE_TRACE_SCRATCH_MB (default 4096; HINGE_TRACE_SCRATCH_BYTES for tests).    */
 int hinge_trace_run(hinge_ctx* ctx, int64_t n, const hinge_cns_alignment* placements, int32_t tspace, int32_t band, int32_t band_max, hinge_cns_alignment* out_alns,
                     uint16_t* trace, int64_t trace_cap, int64_t* n_trace, int32_t* diffs, int32_t* status);
-/* Of the last hinge_trace_run: out[0] batches launched, [1] largest direction scratch of a batch in bytes, [2] placement runs
- * (a widened placement counts once per round), [3] rounds, [4] records made at a W beyond the first, [5] placements without record. */
+/* hinge_trace_run for placements whose end points are APPROXIMATE (chain-level PAF lines, a seeding stage's diagonal and rough
+ * range, slack inherited from read-vs-read overlaps): extend, then clip.  The consumer is the same - the trace as
+ * LAInterface::recoverAlignment reads it (lib/LAInterface.cpp:4125-4244; the record: include/align.h:98-110) - and what this adds
+ * is the part of DALIGNER's Local_Alignment that moves the end points, in a simpler form:
+ *   1. every placement's box is widened per side by e = min(extend, room on A, room on B), the same amount on both sequences (B
+ *      in its strand frame: with comp its room is measured in the complemented frame);
+ *   2. the band of the widened box is filled as for hinge_trace_run (the same kernel, the same rounds, batches and scratch);
+ *   3. of the path's columns - one per step; +match on equal bases, -diff on a substitution, an insertion or a deletion - the
+ *      contiguous run with the largest sum is kept: among equal sums the run that starts latest, among those the one that ends
+ *      latest.  It begins and ends with a matching pair of bases.
+ * The result is a stretch of the band-optimal GLOBAL path of the widened box, not a true local alignment.
+ *   ends             extend 0..32767 (-1 = HINGE_TRACE_EXTEND, else 50); match, diff 1..15 (0 = HINGE_TRACE_MATCH / HINGE_TRACE_DIFF,
+ *                    else 1 / 2); min_score (0 = HINGE_TRACE_MIN_SCORE, else 1).  NULL = all defaults.  HINGE_E_ARG outside.
+ *   out_alns[n]      abpos / aepos / bbpos / bepos REFINED where there is a record (the given ones where there is none);
+ *                    tlen = 2 x the trace-point segments of [abpos', aepos')
+ *   trace, trace_cap must hold two values per segment of every WIDENED placement (HINGE_E_CAPACITY otherwise, before any launch);
+ *                    written: the kept segments only
+ *   diffs[n], score[n]  of the kept run: its edit operations, and match x its matching pairs - diff x its edit operations
+ *   status[2 n]      as hinge_trace_run on the widened box, except: 1 TOUCHED only when a KEPT column lies on the band's first or
+ *                    last diagonal (a clipped tail that wanders to the edge widens nothing); 5 EMPTY - the best sum is below
+ *                    max(1, min_score): no record, final at the W it was seen at.
+ * Everything else - range checks, errors, the scratch budget - as hinge_trace_run.                                               */
+typedef struct hinge_trace_ends {
+    int32_t extend, match, diff, min_score;
+} hinge_trace_ends;
+int hinge_trace_refine(hinge_ctx* ctx, int64_t n, const hinge_cns_alignment* placements, int32_t tspace, int32_t band, int32_t band_max, const hinge_trace_ends* ends,
+                       hinge_cns_alignment* out_alns, uint16_t* trace, int64_t trace_cap, int64_t* n_trace, int32_t* diffs, int32_t* status, int32_t* score);
+/* Of the last hinge_trace_run / hinge_trace_refine: out[0] batches launched, [1] largest direction scratch of a batch in bytes,
+ * [2] placement runs (a widened placement counts once per round), [3] rounds, [4] records made at a W beyond the first, [5]
+ * placements without record, [6] of those, EMPTY ones (hinge_trace_refine). */
 int hinge_trace_last_stats(hinge_ctx* ctx, int64_t* out);
 
 /* Per-kernel timing with HIP events recorded around every launch on the context's stream.

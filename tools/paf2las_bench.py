@@ -7,7 +7,11 @@ not be equal: the generator's path and the banded optimum are different alignmen
 There is no reference program for this step here (DALIGNER is not part of the reference tree): no speed-up factor is claimed.
 Prints one JSON line.
 
-    python tools/paf2las_bench.py [--config cns_bench] [--steps 3] [--band 128] [--band-max 1024] [--no-consensus]
+--ends refine: after the plain run, the same placements with every end point moved by a seeded -80 .. +80 bases (kept inside its
+sequence) through hinge_trace_refine: fill and clip kernel ms, placements/s, and the share of records whose four refined end points
+all lie within 10 bases of the generator's.  A second JSON line.
+
+    python tools/paf2las_bench.py [--config cns_bench] [--steps 3] [--band 128] [--band-max 1024] [--no-consensus] [--ends refine [--extend E]]
 """
 import argparse
 import json
@@ -30,6 +34,9 @@ def main():
     ap.add_argument("--band-max", type=int, default=0)
     ap.add_argument("--no-consensus", action="store_true")
     ap.add_argument("--keep", default="")
+    ap.add_argument("--ends", choices=("given", "refine"), default="given")
+    ap.add_argument("--extend", type=int, default=-1)
+    ap.add_argument("--seed", type=int, default=1)
     args = ap.parse_args()
     import numpy as np
     import consensus_common as cc
@@ -102,9 +109,50 @@ def main():
                 e["bases_differing"] = int((np.frombuffer(x.upper(), np.uint8) != np.frombuffer(y.upper(), np.uint8)).sum())
             cmp_.append(e)
         out["consensus_fasta"] = cmp_
+    print(json.dumps(out))
+    if args.ends == "refine":
+        print(json.dumps(refine_line(args, ctx, d, pl, ts, ksum)))
     if not args.keep:
         shutil.rmtree(wd, ignore_errors=True)
-    print(json.dumps(out))
+
+
+def refine_line(args, ctx, d, pl, ts, plain_kernels_ms):
+    import numpy as np
+    rng = np.random.default_rng(args.seed)
+    alen = np.asarray([len(d.contigs[a]) for a in pl[:, 0]], np.int64)
+    blen = np.asarray([len(d.reads[b]) for b in pl[:, 1]], np.int64)
+    mv = rng.integers(-80, 81, size=(len(pl), 4))
+    pp = pl.copy()
+    pp[:, 3] = np.clip(pl[:, 3] + mv[:, 0], 0, alen)
+    pp[:, 4] = np.clip(pl[:, 4] + mv[:, 1], 0, alen)
+    pp[:, 5] = np.clip(pl[:, 5] + mv[:, 2], 0, blen)
+    pp[:, 6] = np.clip(pl[:, 6] + mv[:, 3], 0, blen)
+    assert (pp[:, 3] < pp[:, 4]).all() and (pp[:, 5] < pp[:, 6]).all()
+    alns, trace, diffs, status, score = ctx.trace_refine(pp, ts, args.band, args.band_max, args.extend)     # warm-up (allocations)
+    out = {"config": args.config, "ends": "refine", "extend": args.extend, "perturbed_by": 80, "seed": args.seed, "placements": int(len(pp)), "stats": ctx.trace_stats()}
+    out["final_w"] = {str(w): int(c) for w, c in zip(*np.unique(status[:, 1], return_counts=True))}
+    out["status"] = {str(s): int(c) for s, c in zip(*np.unique(status[:, 0], return_counts=True))}
+    ctx.profile_enable(4096)
+    t = time.time()
+    for _ in range(args.steps):
+        ctx.trace_refine(pp, ts, args.band, args.band_max, args.extend)
+    call_ms = (time.time() - t) * 1e3 / args.steps
+    rep = ctx.profile_report()
+    out["run_call_ms"] = round(call_ms, 3)
+    out["kernels_ms"] = {k: round(v[0] / args.steps, 4) for k, v in rep.items() if k.startswith("k_trace") and v[1]}
+    out["launches_per_call"] = {k: v[1] // args.steps for k, v in rep.items() if k.startswith("k_trace") and v[1]}
+    ksum = sum(out["kernels_ms"].values())
+    out["placements_per_s_kernels"] = len(pp) / (ksum * 1e-3) if ksum else None
+    out["placements_per_s_call"] = len(pp) / (call_ms * 1e-3)
+    out["kernels_ms_over_plain"] = round(ksum / plain_kernels_ms, 3) if plain_kernels_ms else None
+    ok = status[:, 0] == 0
+    far = np.zeros(len(pp), np.int64)
+    for k, name in enumerate(("abpos", "aepos", "bbpos", "bepos")):
+        far = np.maximum(far, np.abs(alns[name].astype(np.int64) - pl[:, 3 + k]))
+    out["records"] = int(ok.sum())
+    out["share_within_10"] = float((far[ok] <= 10).mean()) if ok.any() else None
+    out["miss_percentiles_50_90_99_max"] = [int(v) for v in np.percentile(far[ok], [50, 90, 99, 100])] if ok.any() else None
+    return out
 
 
 if __name__ == "__main__":
