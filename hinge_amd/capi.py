@@ -115,6 +115,7 @@ SYMBOLS = [
     ("hinge_draft_ladders", C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP]),
     ("hinge_trace_run", C.c_int, [_VP, C.c_int64, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), _VP, _VP]),
     ("hinge_trace_refine", C.c_int, [_VP, C.c_int64, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), _VP, _VP, _VP]),
+    ("hinge_trace_local", C.c_int, [_VP, C.c_int64, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), _VP, _VP, _VP]),
     ("hinge_trace_last_stats", C.c_int, [_VP, _VP]),
     ("hinge_profile_report", C.c_int, [_VP, _VP, _VP]),
     ("hinge_timer_start", C.c_int, [_VP]),
@@ -538,6 +539,15 @@ class Context:
         per edit operation; below max(1, min_score): status 5 EMPTY, no record).  extend -1, match / diff / min_score 0 = the
         defaults (HINGE_TRACE_EXTEND / _MATCH / _DIFF / _MIN_SCORE, else 50, 1, 2, 1).  Returns (alns with the REFINED abpos / aepos /
         bbpos / bepos where there is a record, trace, diffs, status [n, 2], score int32)."""
+        return self._trace_ends(self.lib.hinge_trace_refine, placements, tspace, band, band_max, extend, match, diff, min_score)
+
+    def trace_local(self, placements, tspace: int = 100, band: int = 0, band_max: int = 0, extend: int = -1, match: int = 0, diff: int = 0, min_score: int = 0):
+        """hinge_trace_local (`hinge paf2las --ends local`): trace_refine's arguments and results for placements whose diagonal is
+        approximate too - the best local alignment inside the band of the widened box (Smith-Waterman, linear gap cost), one stretch
+        per placement.  min_score 0 = HINGE_TRACE_MIN_SCORE, else 24; an EMPTY placement runs again at 2 W while that fits band_max."""
+        return self._trace_ends(self.lib.hinge_trace_local, placements, tspace, band, band_max, extend, match, diff, min_score)
+
+    def _trace_ends(self, fn, placements, tspace, band, band_max, extend, match, diff, min_score):
         pl = np.asarray(placements, dtype=np.int64).reshape(-1, 7)
         n = pl.shape[0]
         a = np.zeros(max(n, 1), dtype=CNS_ALN_DTYPE)
@@ -553,16 +563,16 @@ class Context:
         status = np.zeros((max(n, 1), 2), dtype=np.int32)
         nt = C.c_int64(0)
         ends = np.asarray([extend, match, diff, min_score], dtype=np.int32)
-        self._ck(self.lib.hinge_trace_refine(self.h, n, _ptr(a), int(tspace), int(band), int(band_max), _ptr(ends), _ptr(out), _ptr(trace), cap, C.byref(nt), _ptr(diffs),
-                                             _ptr(status), _ptr(score)))
+        self._ck(fn(self.h, n, _ptr(a), int(tspace), int(band), int(band_max), _ptr(ends), _ptr(out), _ptr(trace), cap, C.byref(nt), _ptr(diffs), _ptr(status), _ptr(score)))
         return out[:n], trace[:nt.value], diffs[:n], status[:n], score[:n]
 
     def trace_stats(self) -> dict:
-        """Of the last trace_run / trace_refine: batches, largest direction scratch of a batch (bytes), placement runs, rounds, widened,
-        dropped (placements without record) and, of those, the EMPTY ones of trace_refine."""
+        """Of the last trace_run / trace_refine / trace_local: batches, largest direction scratch of a batch (bytes), placement runs,
+        rounds, widened, dropped (placements without record), of those the EMPTY ones, and the runs of trace_local that went on to
+        2 W because they were EMPTY."""
         st = np.zeros(8, np.int64)
         self._ck(self.lib.hinge_trace_last_stats(self.h, _ptr(st)))
-        return dict(zip(("batches", "scratch_bytes", "runs", "rounds", "widened", "dropped", "empty"), [int(v) for v in st[:7]]))
+        return dict(zip(("batches", "scratch_bytes", "runs", "rounds", "widened", "dropped", "empty", "empty_widened"), [int(v) for v in st[:8]]))
 
     def profile_enable(self, max_launches: int):
         self._ck(self.lib.hinge_profile_enable(self.h, int(max_launches)))

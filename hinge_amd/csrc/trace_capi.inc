@@ -4,16 +4,18 @@
 // round under the direction-scratch budget, the launches, the results back in the caller's order.  The kernels: trace_kernels.h.
 constexpr int TRACE_ROUNDS = 9;
 
+enum TraceMode { TRACE_MODE_RUN = 0, TRACE_MODE_REFINE = 1, TRACE_MODE_LOCAL = 2 };   // hinge_trace_run / _refine / _local
+
 struct TraceState {
-    DevBuf jobs, dirs, trace, status, diffs, cost, clip, score;
-    size_t lds_attr = 0;
+    DevBuf jobs, dirs, trace, status, diffs, cost, clip, score, best;
+    size_t lds_attr = 0, lds_attr_local = 0;        // hipFuncAttributeMaxDynamicSharedMemorySize is per kernel: k_trace_fill, k_trace_fill_local
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // hinge_trace_last_stats
 };
 
 static void trace_release(hinge_ctx* ctx) {
     TraceState* t = ctx->trace_st;
     if (!t) return;
-    DevBuf* all[] = {&t->jobs, &t->dirs, &t->trace, &t->status, &t->diffs, &t->cost, &t->clip, &t->score};
+    DevBuf* all[] = {&t->jobs, &t->dirs, &t->trace, &t->status, &t->diffs, &t->cost, &t->clip, &t->score, &t->best};
     for (DevBuf* b : all) release(*b);
     delete t;
     ctx->trace_st = nullptr;
@@ -25,8 +27,9 @@ static long long trace_env(const char* name, long long def) {
 }
 
 // One batch: jobs[0..nj) (dir_off / trace_off laid out by the caller) at half-width W.  Results to the host vectors.
-// ends == nullptr: k_trace_walk; else k_trace_clip in its place, with the kept cells and the scores back as well.
-static int trace_batch(hinge_ctx* ctx, const std::vector<TraceJob>& jobs, long long dir_words, long long n_vals, int W, int tspace, const hinge_trace_ends* ends,
+// TRACE_MODE_RUN: k_trace_fill, k_trace_walk; _REFINE: k_trace_clip in the walk's place, with the kept cells and the scores back as
+// well; _LOCAL: k_trace_fill_local, k_trace_walk_local, the same results back as _REFINE.  ends: null for _RUN only.
+static int trace_batch(hinge_ctx* ctx, const std::vector<TraceJob>& jobs, long long dir_words, long long n_vals, int W, int tspace, int mode, const hinge_trace_ends* ends,
                        std::vector<unsigned short>& h_trace, std::vector<int>& h_status, std::vector<int>& h_diffs, std::vector<int>& h_clip, std::vector<int>& h_score) {
     TraceState* t = ctx->trace_st;
     CnsState* s = ctx->cns;
@@ -42,6 +45,7 @@ static int trace_batch(hinge_ctx* ctx, const std::vector<TraceJob>& jobs, long l
         if ((rc = ensure(ctx, t->clip, sizeof(int) * 4 * nj))) return rc;
         if ((rc = ensure(ctx, t->score, sizeof(int) * nj))) return rc;
     }
+    if (mode == TRACE_MODE_LOCAL && (rc = ensure(ctx, t->best, sizeof(int) * 3 * nj))) return rc;
     CK(hipMemcpyAsync(t->jobs.p, jobs.data(), sizeof(TraceJob) * nj, hipMemcpyHostToDevice, ctx->stream));
     // poison: a slot no kernel wrote is seen as such, never as data (0xff bytes: status / diffs / cost -1, trace 0xffff)
     CK(hipMemsetAsync(t->trace.p, 0xff, sizeof(unsigned short) * (size_t)std::max<long long>(n_vals, 1), ctx->stream));
@@ -52,25 +56,42 @@ static int trace_batch(hinge_ctx* ctx, const std::vector<TraceJob>& jobs, long l
         CK(hipMemsetAsync(t->clip.p, 0xff, sizeof(int) * 4 * nj, ctx->stream));
         CK(hipMemsetAsync(t->score.p, 0xff, sizeof(int) * nj, ctx->stream));
     }
+    if (mode == TRACE_MODE_LOCAL) CK(hipMemsetAsync(t->best.p, 0xff, sizeof(int) * 3 * nj, ctx->stream));
     const size_t lds = trace_lds_bytes(W);
-    if (lds > 48 * 1024 && lds > t->lds_attr) {
+    if (mode == TRACE_MODE_LOCAL) {
+        if (lds > 48 * 1024 && lds > t->lds_attr_local) {
+            CK(hipFuncSetAttribute((const void*)k_trace_fill_local, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            t->lds_attr_local = lds;
+        }
+    } else if (lds > 48 * 1024 && lds > t->lds_attr) {
         CK(hipFuncSetAttribute((const void*)k_trace_fill, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         t->lds_attr = lds;
     }
     CnsSeqs SA{(const unsigned char*)s->bps[0].p, (const long long*)s->boff[0].p, (const int*)s->rlen[0].p};
     CnsSeqs SB{(const unsigned char*)s->bps[1].p, (const long long*)s->boff[1].p, (const int*)s->rlen[1].p};
-    {
+    const int tmax = tspace <= 125 ? 255 : 65534;
+    const unsigned walk_blocks = (unsigned)((nj + 63) / 64);
+    if (mode == TRACE_MODE_LOCAL) {
+        ProfScope _ps(ctx, KID_TRACE_FILL_LOCAL);
+        hipLaunchKernelGGL(k_trace_fill_local, dim3((unsigned)nj), dim3(64), lds, ctx->stream, SA, SB, (const TraceJob*)t->jobs.p, (int)nj, W, (int)ends->match, (int)ends->diff,
+                           (unsigned*)t->dirs.p, (int*)t->best.p);
+    } else {
         ProfScope _ps(ctx, KID_TRACE_FILL);
         hipLaunchKernelGGL(k_trace_fill, dim3((unsigned)nj), dim3(64), lds, ctx->stream, SA, SB, (const TraceJob*)t->jobs.p, (int)nj, W, (unsigned*)t->dirs.p, (int*)t->cost.p);
     }
-    if (ends) {
+    if (mode == TRACE_MODE_LOCAL) {
+        ProfScope _ps(ctx, KID_TRACE_WALK_LOCAL);
+        hipLaunchKernelGGL(k_trace_walk_local, dim3(walk_blocks), dim3(64), 0, ctx->stream, (const TraceJob*)t->jobs.p, (int)nj, W, tspace, tmax, (int)ends->match, (int)ends->diff,
+                           (int)ends->min_score, trace_local_margin(W), (const unsigned*)t->dirs.p, (const int*)t->best.p, (unsigned short*)t->trace.p, (int*)t->diffs.p,
+                           (int*)t->status.p, (int*)t->clip.p, (int*)t->score.p);
+    } else if (mode == TRACE_MODE_REFINE) {
         ProfScope _ps(ctx, KID_TRACE_CLIP);
-        hipLaunchKernelGGL(k_trace_clip, dim3((unsigned)((nj + 63) / 64)), dim3(64), 0, ctx->stream, (const TraceJob*)t->jobs.p, (int)nj, W, tspace, tspace <= 125 ? 255 : 65534,
+        hipLaunchKernelGGL(k_trace_clip, dim3(walk_blocks), dim3(64), 0, ctx->stream, (const TraceJob*)t->jobs.p, (int)nj, W, tspace, tmax,
                            (int)ends->match, (int)ends->diff, (int)ends->min_score, (const unsigned*)t->dirs.p, (const int*)t->cost.p, (unsigned short*)t->trace.p, (int*)t->diffs.p,
                            (int*)t->status.p, (int*)t->clip.p, (int*)t->score.p);
     } else {
         ProfScope _ps(ctx, KID_TRACE_WALK);
-        hipLaunchKernelGGL(k_trace_walk, dim3((unsigned)((nj + 63) / 64)), dim3(64), 0, ctx->stream, (const TraceJob*)t->jobs.p, (int)nj, W, tspace, tspace <= 125 ? 255 : 65534,
+        hipLaunchKernelGGL(k_trace_walk, dim3(walk_blocks), dim3(64), 0, ctx->stream, (const TraceJob*)t->jobs.p, (int)nj, W, tspace, tmax,
                            (const unsigned*)t->dirs.p, (const int*)t->cost.p, (unsigned short*)t->trace.p, (int*)t->diffs.p, (int*)t->status.p);
     }
     CK(hipGetLastError());
@@ -90,8 +111,9 @@ static int trace_batch(hinge_ctx* ctx, const std::vector<TraceJob>& jobs, long l
     return HINGE_OK;
 }
 
-// hinge_trace_run (ends == nullptr) and hinge_trace_refine (ends: extend, match, diff, min_score, all resolved) share everything
-// but the box a placement runs in, the second kernel of a batch, and what of a job's slots is a record's.
+// hinge_trace_run (ends == nullptr), hinge_trace_refine and hinge_trace_local (ends: extend, match, diff, min_score, all resolved)
+// share everything but the box a placement runs in, the kernels of a batch, what of a job's slots is a record's, and - local -
+// that an EMPTY placement goes on to 2 W like a NO_PATH one (a diagonal off by more than W leaves nothing of it in the band).
 struct TraceOut {                       // the caller's output arrays (score: hinge_trace_refine only)
     hinge_cns_alignment* alns;
     uint16_t* trace;
@@ -101,7 +123,7 @@ struct TraceOut {                       // the caller's output arrays (score: hi
 };
 
 static int trace_call(hinge_ctx* ctx, const char* who, int64_t n, const hinge_cns_alignment* placements, int32_t tspace, int32_t band, int32_t band_max,
-                      const hinge_trace_ends* ends, const TraceOut& out) {
+                      int mode, const hinge_trace_ends* ends, const TraceOut& out) {
     hinge_cns_alignment* const out_alns = out.alns;
     uint16_t* const trace = out.trace;
     const int64_t trace_cap = out.trace_cap;
@@ -189,7 +211,7 @@ static int trace_call(hinge_ctx* ctx, const char* who, int64_t n, const hinge_cn
             }
             if (jobs.empty()) continue;
             int rc;
-            if ((rc = trace_batch(ctx, jobs, words, vals, W, tspace, ends, h_trace, h_status, h_diffs, h_clip, h_score))) return rc;
+            if ((rc = trace_batch(ctx, jobs, words, vals, W, tspace, mode, ends, h_trace, h_status, h_diffs, h_clip, h_score))) return rc;
             t->stats[0]++;
             t->stats[1] = std::max<int64_t>(t->stats[1], words * (int64_t)sizeof(unsigned));
             t->stats[2] += (int64_t)jobs.size();
@@ -217,6 +239,7 @@ static int trace_call(hinge_ctx* ctx, const char* who, int64_t n, const hinge_cn
                     tr[(size_t)x].assign(p, p + 2 * cnt);
                     for (unsigned short v : tr[(size_t)x]) if (v == TRACE_POISON16) return fail(ctx, HINGE_E_DEVICE, me(": a trace slot was never written"));
                 } else if ((code == TRACE_ST_TOUCHED || code == TRACE_ST_NO_PATH) && !last) next.push_back(x);
+                else if (code == TRACE_ST_EMPTY && mode == TRACE_MODE_LOCAL && !last) { next.push_back(x); t->stats[7]++; }
             }
         }
         std::sort(next.begin(), next.end());
@@ -252,7 +275,7 @@ extern "C" {
 
 int hinge_trace_run(hinge_ctx* ctx, int64_t n, const hinge_cns_alignment* placements, int32_t tspace, int32_t band, int32_t band_max, hinge_cns_alignment* out_alns,
                     uint16_t* trace, int64_t trace_cap, int64_t* n_trace, int32_t* diffs, int32_t* status) {
-    return trace_call(ctx, "hinge_trace_run", n, placements, tspace, band, band_max, nullptr, TraceOut{out_alns, trace, trace_cap, n_trace, diffs, status, nullptr});
+    return trace_call(ctx, "hinge_trace_run", n, placements, tspace, band, band_max, TRACE_MODE_RUN, nullptr, TraceOut{out_alns, trace, trace_cap, n_trace, diffs, status, nullptr});
 }
 
 int hinge_trace_refine(hinge_ctx* ctx, int64_t n, const hinge_cns_alignment* placements, int32_t tspace, int32_t band, int32_t band_max, const hinge_trace_ends* ends,
@@ -264,7 +287,19 @@ int hinge_trace_refine(hinge_ctx* ctx, int64_t n, const hinge_cns_alignment* pla
     if (e.min_score == 0) e.min_score = (int32_t)trace_env("HINGE_TRACE_MIN_SCORE", 1);
     if (e.extend < 0 || e.extend > 32767 || e.match < 1 || e.match > 15 || e.diff < 1 || e.diff > 15)
         return fail(ctx, HINGE_E_ARG, "hinge_trace_refine: extend must lie in 0..32767 (-1 = the default), match and diff in 1..15 (0 = the default)");
-    return trace_call(ctx, "hinge_trace_refine", n, placements, tspace, band, band_max, &e, TraceOut{out_alns, trace, trace_cap, n_trace, diffs, status, score});
+    return trace_call(ctx, "hinge_trace_refine", n, placements, tspace, band, band_max, TRACE_MODE_REFINE, &e, TraceOut{out_alns, trace, trace_cap, n_trace, diffs, status, score});
+}
+
+int hinge_trace_local(hinge_ctx* ctx, int64_t n, const hinge_cns_alignment* placements, int32_t tspace, int32_t band, int32_t band_max, const hinge_trace_ends* ends,
+                      hinge_cns_alignment* out_alns, uint16_t* trace, int64_t trace_cap, int64_t* n_trace, int32_t* diffs, int32_t* status, int32_t* score) {
+    hinge_trace_ends e = ends ? *ends : hinge_trace_ends{-1, 0, 0, 0};
+    if (e.extend == -1) e.extend = (int32_t)trace_env("HINGE_TRACE_EXTEND", 50);
+    if (e.match == 0) e.match = (int32_t)trace_env("HINGE_TRACE_MATCH", 1);
+    if (e.diff == 0) e.diff = (int32_t)trace_env("HINGE_TRACE_DIFF", 2);
+    if (e.min_score == 0) e.min_score = (int32_t)trace_env("HINGE_TRACE_MIN_SCORE", HINGE_TRACE_LOCAL_MIN_SCORE);
+    if (e.extend < 0 || e.extend > 32767 || e.match < 1 || e.match > 15 || e.diff < 1 || e.diff > 15)
+        return fail(ctx, HINGE_E_ARG, "hinge_trace_local: extend must lie in 0..32767 (-1 = the default), match and diff in 1..15 (0 = the default)");
+    return trace_call(ctx, "hinge_trace_local", n, placements, tspace, band, band_max, TRACE_MODE_LOCAL, &e, TraceOut{out_alns, trace, trace_cap, n_trace, diffs, status, score});
 }
 
 int hinge_trace_last_stats(hinge_ctx* ctx, int64_t* out) {

@@ -1,5 +1,5 @@
 // paf2las  ==  `hinge paf2las DRAFT_DB READ_DB PAF OUT.las [--band W] [--band-max W] [--tspace T] [--draft-names FASTA] [--read-names FASTA]
-//                                [--ends given|refine] [--extend E] [--scores M,X] [--min-score S]`
+//                                [--ends given|refine|local] [--extend E] [--scores M,X] [--min-score S]`
 // Not a program of the reference: it stands where demo/ecoli_demo/run.sh:30-37 runs HPC.daligner + LAmerge on (draft, reads) to get
 // the draft-vs-reads .las WITH trace points that `hinge consensus` needs.  Input: placements as PAF, query = read, target =
 // contig (what `minimap2 draft.fasta reads.fasta` prints).  The base-level alignment between the given end points and its trace
@@ -7,7 +7,8 @@
 // resolves names, and writes the .las (align.h:98-110: the records `Read_Overlap` reads).
 // --ends given (the default): the PAF's end points are exact (hinge_trace_run).  --ends refine: they are approximate - every
 // placement is widened by up to E bases per side and the best-scoring stretch of its path is kept (hinge_trace_refine); the
-// records carry the refined end points.
+// records carry the refined end points.  --ends local: the diagonal is approximate too (all four end points off independently) -
+// the best local alignment inside the band of the widened box is kept (hinge_trace_local); --extend, --scores and --min-score apply.
 #include "host_common.h"
 
 #include <map>
@@ -17,7 +18,7 @@ using namespace hh;
 
 static void usage() {
     fprintf(stderr, "usage: paf2las <draft db> <read db> <paf> <out.las> [--band W] [--band-max W] [--tspace T] [--draft-names FASTA] [--read-names FASTA]\n"
-                    "               [--ends given|refine] [--extend E] [--scores M,X] [--min-score S]\n");
+                    "               [--ends given|refine|local] [--extend E] [--scores M,X] [--min-score S]\n");
 }
 
 // first word of every header of a FASTA file -> record index
@@ -52,7 +53,7 @@ int main(int argc, char* argv[]) {
     std::vector<std::string> pos;
     int band = 0, band_max = 0, tspace = 100;
     std::string draft_names, read_names, ends_mode = "given";
-    hinge_trace_ends ends = {-1, 0, 0, 0};          // the library's defaults (50; 1, 2; 1)
+    hinge_trace_ends ends = {-1, 0, 0, 0};          // the library's defaults (50; 1, 2; refine 1, local 24)
     bool ends_opts = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -77,9 +78,10 @@ int main(int argc, char* argv[]) {
         else pos.push_back(a);
     }
     if (pos.size() != 4 || tspace <= 0 || tspace > 32767 || band < 0 || band_max < 0) { usage(); return 1; }
-    if (ends_mode != "given" && ends_mode != "refine") { fprintf(stderr, "paf2las: --ends takes given or refine\n"); usage(); return 1; }
-    const bool refine = ends_mode == "refine";
-    if (ends_opts && !refine) { fprintf(stderr, "paf2las: --extend, --scores and --min-score belong to --ends refine\n"); usage(); return 1; }
+    if (ends_mode != "given" && ends_mode != "refine" && ends_mode != "local") { fprintf(stderr, "paf2las: --ends takes given or refine or local\n"); usage(); return 1; }
+    const bool local = ends_mode == "local";
+    const bool refine = ends_mode == "refine" || local;      // everything below that refined end points need
+    if (ends_opts && !refine) { fprintf(stderr, "paf2las: --extend, --scores and --min-score belong to --ends refine and --ends local\n"); usage(); return 1; }
     PhaseTimer tm("paf2las");
     CtxInit gpu;
     gpu.start();
@@ -164,7 +166,8 @@ int main(int argc, char* argv[]) {
     int64_t n_trace = 0;
     if (refine) {
         std::vector<int32_t> score((size_t)std::max<int64_t>(n, 1));
-        if (hinge_trace_refine(ctx, n, pl.data(), tspace, band, band_max, &ends, out.data(), trace.data(), cap, &n_trace, diffs.data(), status.data(), score.data()) != HINGE_OK)
+        if ((local ? hinge_trace_local : hinge_trace_refine)(ctx, n, pl.data(), tspace, band, band_max, &ends, out.data(), trace.data(), cap, &n_trace, diffs.data(), status.data(),
+                                                             score.data()) != HINGE_OK)
             die("trace");
     } else if (hinge_trace_run(ctx, n, pl.data(), tspace, band, band_max, out.data(), trace.data(), cap, &n_trace, diffs.data(), status.data()) != HINGE_OK) die("trace");
     tm.mark("align + trace");

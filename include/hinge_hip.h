@@ -410,7 +410,7 @@ int hinge_draft_ladders(hinge_ctx* ctx, int64_t n_ladders, const int64_t* rung_o
  * such placements, the trace output of DALIGNER's Local_Alignment as LAInterface::recoverAlignment consumes it
  * (lib/LAInterface.cpp:4125-4244; the record: include/align.h:98-110): per tspace block of A the pair (edit operations, B
  * bases).  NOT replaced: finding the placements (seeding, chaining).  hinge_trace_run takes the end points as exact;
- * hinge_trace_refine below extends and clips approximate ones.
+ * hinge_trace_refine below extends and clips approximate ones; hinge_trace_local aligns locally inside the band.
  * Uses the two DBs given by hinge_consensus_set_db (0 = draft, 1 = reads).
  *   placements[n]    aread, bread, comp, abpos, aepos, bbpos, bepos as in hinge_cns_alignment (B in the complemented frame when
  *                    comp); tlen and trace_off are ignored
@@ -459,9 +459,33 @@ typedef struct hinge_trace_ends {
 } hinge_trace_ends;
 int hinge_trace_refine(hinge_ctx* ctx, int64_t n, const hinge_cns_alignment* placements, int32_t tspace, int32_t band, int32_t band_max, const hinge_trace_ends* ends,
                        hinge_cns_alignment* out_alns, uint16_t* trace, int64_t trace_cap, int64_t* n_trace, int32_t* diffs, int32_t* status, int32_t* score);
-/* Of the last hinge_trace_run / hinge_trace_refine: out[0] batches launched, [1] largest direction scratch of a batch in bytes,
- * [2] placement runs (a widened placement counts once per round), [3] rounds, [4] records made at a W beyond the first, [5]
- * placements without record, [6] of those, EMPTY ones (hinge_trace_refine). */
+/* hinge_trace_refine's signature for placements whose DIAGONAL is approximate as well (all four end points off independently:
+ * chain-level PAF lines, a seeding stage's diagonal and rough range).  A stretch of the global path must pay gaps to reach the
+ * box's corners and loses the alignment's first and last bases to them; this is a true local alignment, with no corner to reach:
+ *   1. the box is widened as for hinge_trace_refine;
+ *   2. Smith-Waterman inside the band of the widened box (the same band, rounds, batches and scratch), linear gap cost:
+ *      H(i, j) = max(0, H(i - 1, j - 1) + (equal ? +match : -diff), H(i - 1, j) - diff, H(i, j - 1) - diff); row 0, column 0 and
+ *      cells outside the band read as 0.  Ties of a cell: 0, then diagonal, gap in B, gap in A;
+ *   3. kept: the path from the best cell (the largest H; of equal ones the smallest i + j, of those the smallest i) back to the
+ *      first cell with H = 0.
+ * Claimed: the optimal local alignment WITHIN THE BAND, linear gap cost, ONE stretch per placement.  Not claimed: seeding (a
+ * placement must bring its diagonal to within band_max), a second stretch of the same placement, affine gaps.
+ *   ends             as hinge_trace_refine, except min_score: 0 = HINGE_TRACE_MIN_SCORE, else HINGE_TRACE_LOCAL_MIN_SCORE = 24 (the
+ *                    largest local score of 16 unrelated 7128 x 7128 pairs - the bench's mean placement - at W = 1024 under the
+ *                    default scores was 16; plus half.  With 1, every unrelated pair would get a junk record)
+ *   status[2 n]      as hinge_trace_refine, except: 1 TOUCHED when a kept column lies within min(3, W / 2) diagonals of the band's
+ *                    first or last one (a stretch the band cuts ends on its last match BEFORE the edge); 5 EMPTY - no cell of
+ *                    the band scores max(1, min_score) - is final only at the last W: before that the placement runs again at 2 W
+ *                    like a NO_PATH one (a diagonal off by more than W leaves nothing of it in the band).  The price: an unrelated
+ *                    placement pays every round.
+ * Everything else - outputs, range checks, errors, the scratch budget - as hinge_trace_refine.                                  */
+#define HINGE_TRACE_LOCAL_MIN_SCORE 24
+int hinge_trace_local(hinge_ctx* ctx, int64_t n, const hinge_cns_alignment* placements, int32_t tspace, int32_t band, int32_t band_max, const hinge_trace_ends* ends,
+                      hinge_cns_alignment* out_alns, uint16_t* trace, int64_t trace_cap, int64_t* n_trace, int32_t* diffs, int32_t* status, int32_t* score);
+/* Of the last hinge_trace_run / hinge_trace_refine / hinge_trace_local: out[0] batches launched, [1] largest direction scratch of a
+ * batch in bytes, [2] placement runs (a widened placement counts once per round), [3] rounds, [4] records made at a W beyond the
+ * first, [5] placements without record, [6] of those, EMPTY ones (hinge_trace_refine, hinge_trace_local), [7] placement runs that
+ * went on to 2 W because they were EMPTY (hinge_trace_local). */
 int hinge_trace_last_stats(hinge_ctx* ctx, int64_t* out);
 
 /* Per-kernel timing with HIP events recorded around every launch on the context's stream.

@@ -9,9 +9,11 @@ Prints one JSON line.
 
 --ends refine: after the plain run, the same placements with every end point moved by a seeded -80 .. +80 bases (kept inside its
 sequence) through hinge_trace_refine: fill and clip kernel ms, placements/s, and the share of records whose four refined end points
-all lie within 10 bases of the generator's.  A second JSON line.
+all lie within 10 bases of the generator's, with the miss percentiles.  A second JSON line.
+--ends local: the same perturbed placements through hinge_trace_local (k_trace_fill_local, k_trace_walk_local), the same figures;
+`--ends refine local` gives both lines from one session.
 
-    python tools/paf2las_bench.py [--config cns_bench] [--steps 3] [--band 128] [--band-max 1024] [--no-consensus] [--ends refine [--extend E]]
+    python tools/paf2las_bench.py [--config cns_bench] [--steps 3] [--band 128] [--band-max 1024] [--no-consensus] [--ends refine|local ... [--extend E]]
 """
 import argparse
 import json
@@ -34,7 +36,7 @@ def main():
     ap.add_argument("--band-max", type=int, default=0)
     ap.add_argument("--no-consensus", action="store_true")
     ap.add_argument("--keep", default="")
-    ap.add_argument("--ends", choices=("given", "refine"), default="given")
+    ap.add_argument("--ends", choices=("given", "refine", "local"), nargs="+", default=["given"])
     ap.add_argument("--extend", type=int, default=-1)
     ap.add_argument("--seed", type=int, default=1)
     args = ap.parse_args()
@@ -110,14 +112,16 @@ def main():
             cmp_.append(e)
         out["consensus_fasta"] = cmp_
     print(json.dumps(out))
-    if args.ends == "refine":
-        print(json.dumps(refine_line(args, ctx, d, pl, ts, ksum)))
+    for mode in args.ends:
+        if mode != "given":
+            print(json.dumps(refine_line(args, ctx, d, pl, ts, ksum, mode)))
     if not args.keep:
         shutil.rmtree(wd, ignore_errors=True)
 
 
-def refine_line(args, ctx, d, pl, ts, plain_kernels_ms):
+def refine_line(args, ctx, d, pl, ts, plain_kernels_ms, mode):
     import numpy as np
+    run = ctx.trace_local if mode == "local" else ctx.trace_refine
     rng = np.random.default_rng(args.seed)
     alen = np.asarray([len(d.contigs[a]) for a in pl[:, 0]], np.int64)
     blen = np.asarray([len(d.reads[b]) for b in pl[:, 1]], np.int64)
@@ -128,14 +132,14 @@ def refine_line(args, ctx, d, pl, ts, plain_kernels_ms):
     pp[:, 5] = np.clip(pl[:, 5] + mv[:, 2], 0, blen)
     pp[:, 6] = np.clip(pl[:, 6] + mv[:, 3], 0, blen)
     assert (pp[:, 3] < pp[:, 4]).all() and (pp[:, 5] < pp[:, 6]).all()
-    alns, trace, diffs, status, score = ctx.trace_refine(pp, ts, args.band, args.band_max, args.extend)     # warm-up (allocations)
-    out = {"config": args.config, "ends": "refine", "extend": args.extend, "perturbed_by": 80, "seed": args.seed, "placements": int(len(pp)), "stats": ctx.trace_stats()}
+    alns, trace, diffs, status, score = run(pp, ts, args.band, args.band_max, args.extend)     # warm-up (allocations)
+    out = {"config": args.config, "ends": mode, "extend": args.extend, "perturbed_by": 80, "seed": args.seed, "placements": int(len(pp)), "stats": ctx.trace_stats()}
     out["final_w"] = {str(w): int(c) for w, c in zip(*np.unique(status[:, 1], return_counts=True))}
     out["status"] = {str(s): int(c) for s, c in zip(*np.unique(status[:, 0], return_counts=True))}
     ctx.profile_enable(4096)
     t = time.time()
     for _ in range(args.steps):
-        ctx.trace_refine(pp, ts, args.band, args.band_max, args.extend)
+        run(pp, ts, args.band, args.band_max, args.extend)
     call_ms = (time.time() - t) * 1e3 / args.steps
     rep = ctx.profile_report()
     out["run_call_ms"] = round(call_ms, 3)
