@@ -45,7 +45,7 @@ int hinge_consensus_set_db(hinge_ctx* ctx, int32_t which, int32_t n, const int32
     if (!ctx->cns) ctx->cns = new CnsState();
     CnsState* s = ctx->cns;
     int rc;
-    if ((rc = ensure(ctx, s->bps[which], (size_t)bps_bytes + 8))) return rc;
+    if ((rc = ensure(ctx, s->bps[which], (size_t)bps_bytes + CNS_BPS_SPARE))) return rc;     // (cns_window's loads end inside the spare bytes)
     if ((rc = ensure(ctx, s->boff[which], sizeof(long long) * (size_t)std::max(n, 1)))) return rc;
     if ((rc = ensure(ctx, s->rlen[which], sizeof(int) * (size_t)std::max(n, 1)))) return rc;
     if (bps_bytes) CK(hipMemcpyAsync(s->bps[which].p, bps, (size_t)bps_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -209,62 +209,68 @@ int hinge_consensus_run(hinge_ctx* ctx, int64_t n_aln, const hinge_cns_alignment
     }
     CK(hipMemcpyAsync(s->cbase.p, s->h_cbase.data(), sizeof(long long) * ((size_t)n_contigs + 1), hipMemcpyHostToDevice, ctx->stream));
     if (s->n_blocks) CK(hipMemcpyAsync(s->contig_of_block.p, cob.data(), sizeof(int2) * (size_t)s->n_blocks, hipMemcpyHostToDevice, ctx->stream));
-    if (!tiled || s->n_seg == 0) CK(hipMemsetAsync(s->counts.p, 0, sizeof(int) * 9 * plane, ctx->stream));   // (the tile vote stores every position itself)
-    CK(hipMemsetAsync(s->stats.p, 0, sizeof(CnsStats) * (size_t)std::max(n_contigs, 1), ctx->stream));
-    unsigned long long* total = (unsigned long long*)((char*)s->scal.p + 8);
-    CnsSeqs SA{(const unsigned char*)s->bps[0].p, (const long long*)s->boff[0].p, (const int*)s->rlen[0].p};
-    CnsSeqs SB{(const unsigned char*)s->bps[1].p, (const long long*)s->boff[1].p, (const int*)s->rlen[1].p};
-    if (s->n_seg) {
-        {
-            ProfScope _ps(ctx, KID_CNS_COLUMNS);
-            hipLaunchKernelGGL(k_cns_columns, dim3((unsigned)((n_aln + CNS_BLOCK - 1) / CNS_BLOCK)), dim3(CNS_BLOCK), 0, ctx->stream, (const CnsAln*)s->alns.p, (int)n_aln,
-                               (const CnsSeg*)s->segs.p, (const int*)s->indels.p, (const int*)s->n_indel.p, (const int*)s->n_ins.p, (int*)s->col_base.p, (CnsCols*)s->cols.p, 100);
-        }
-        if (tiled) {
-            const size_t lds = sizeof(unsigned) * 5 * ((size_t)tile + 1);
-            if (lds > 48 * 1024 && lds > s->vote_lds_attr) {
-                CK(hipFuncSetAttribute((const void*)k_cns_vote_tiles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                s->vote_lds_attr = lds;
-            }
-            ProfScope _ps(ctx, KID_CNS_VOTE);
-            const unsigned galn = (unsigned)((n_aln + CNS_BLOCK - 1) / CNS_BLOCK);
-            hipLaunchKernelGGL(k_cns_tile_count, dim3(galn), dim3(CNS_BLOCK), 0, ctx->stream, (const CnsAln*)s->alns.p, (int)n_aln, (const CnsSeg*)s->segs.p,
-                               (const int*)s->tile_base.p, tile, (unsigned*)s->tile_ptr.p);
-            hipLaunchKernelGGL(k_cns_scan, dim3(1), dim3(1024), 0, ctx->stream, (unsigned*)s->tile_ptr.p, n_tiles + 1, total + 1);
-            CK(hipMemcpyAsync(s->tile_cursor.p, s->tile_ptr.p, sizeof(unsigned) * ((size_t)n_tiles + 1), hipMemcpyDeviceToDevice, ctx->stream));
-            hipLaunchKernelGGL(k_cns_tile_fill, dim3(galn), dim3(CNS_BLOCK), 0, ctx->stream, (const CnsAln*)s->alns.p, (int)n_aln, (const CnsSeg*)s->segs.p,
-                               (const int*)s->tile_base.p, tile, (unsigned*)s->tile_cursor.p, (int*)s->seg_order.p);
-            hipLaunchKernelGGL(k_cns_vote_tiles, dim3((unsigned)n_tiles), dim3(CNS_BLOCK), lds, ctx->stream, SB, (const CnsAln*)s->alns.p, (const CnsSeg*)s->segs.p,
-                               (const int*)s->indels.p, (const int*)s->n_indel.p, (const int*)s->col_base.p, (const CnsCols*)s->cols.p, (const long long*)s->cbase.p,
-                               (const int*)s->tile_base.p, (const int*)s->contig_of_tile.p, (const unsigned*)s->tile_ptr.p, (const int*)s->seg_order.p, tile,
-                               (int*)s->counts.p, (long long)plane, (int*)s->halo.p);
-        } else {
-            ProfScope _ps(ctx, KID_CNS_VOTE);
-            hipLaunchKernelGGL(k_cns_vote, dim3((unsigned)((s->n_seg + CNS_BLOCK - 1) / CNS_BLOCK)), dim3(CNS_BLOCK), 0, ctx->stream, SB, (const CnsAln*)s->alns.p,
-                               (const CnsSeg*)s->segs.p, (int)s->n_seg, (const int*)s->indels.p, (const int*)s->n_indel.p, (const int*)s->col_base.p, (const CnsCols*)s->cols.p,
-                               (const long long*)s->cbase.p, (int*)s->counts.p, (long long)plane);
-        }
-    }
-    if (s->n_blocks) {
-        ProfScope _ps(ctx, KID_CNS_CALL);
-        hipLaunchKernelGGL(k_cns_call, dim3((unsigned)s->n_blocks), dim3(CNS_BLOCK), 0, ctx->stream, SA, (const int*)s->counts.p, (long long)plane, (long long)s->n_pos,
-                           (const int2*)s->contig_of_block.p, (const long long*)s->cbase.p, (unsigned*)s->packed.p, (unsigned*)s->block_sum.p, (CnsStats*)s->stats.p,
-                           (tiled && s->n_seg) ? (const int*)s->halo.p : (const int*)nullptr, (const int*)s->tile_base.p, tile);
-        hipLaunchKernelGGL(k_cns_scan, dim3(1), dim3(1024), 0, ctx->stream, (unsigned*)s->block_sum.p, s->n_blocks, total);
-        hipLaunchKernelGGL(k_cns_emit, dim3((unsigned)s->n_blocks), dim3(CNS_BLOCK), 0, ctx->stream, (const unsigned*)s->packed.p, (const int2*)s->contig_of_block.p,
-                           (const long long*)s->cbase.p, (const unsigned*)s->block_sum.p, (char*)s->out.p);
-    }
-    CK(hipGetLastError());
-    // results to the host: the strings, the block offsets (where a contig's string starts), statistics, chop offsets
     unsigned long long scal_h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    CK(hipMemcpyAsync(scal_h, s->scal.p, 64, hipMemcpyDeviceToHost, ctx->stream));
-    s->h_block_off.assign((size_t)s->n_blocks + 1, 0);
-    if (s->n_blocks) CK(hipMemcpyAsync(s->h_block_off.data(), s->block_sum.p, sizeof(unsigned) * (size_t)s->n_blocks, hipMemcpyDeviceToHost, ctx->stream));
-    s->h_stats.assign((size_t)std::max(n_contigs, 1), CnsStats{});
-    if (n_contigs) CK(hipMemcpyAsync(s->h_stats.data(), s->stats.p, sizeof(CnsStats) * (size_t)n_contigs, hipMemcpyDeviceToHost, ctx->stream));
-    s->h_cols.assign((size_t)std::max<int64_t>(n_aln, 1), CnsCols{});
-    if (n_aln) CK(hipMemcpyAsync(s->h_cols.data(), s->cols.p, sizeof(CnsCols) * (size_t)n_aln, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
+    // The vote, the calls and the results.  A second pass only where the tile vote reports CNS_ST_VOTE16 (an inserted-base counter stood
+    // at 0xffff: tens of thousands of inserted bases at one position): the planes are zeroed and k_cns_vote votes with its int32 counters.
+    for (int pass = 0;; pass++) {
+        if (!tiled || s->n_seg == 0) CK(hipMemsetAsync(s->counts.p, 0, sizeof(int) * 9 * plane, ctx->stream));   // (the tile vote stores every position itself)
+        CK(hipMemsetAsync(s->stats.p, 0, sizeof(CnsStats) * (size_t)std::max(n_contigs, 1), ctx->stream));
+        unsigned long long* total = (unsigned long long*)((char*)s->scal.p + 8);
+        CnsSeqs SA{(const unsigned char*)s->bps[0].p, (const long long*)s->boff[0].p, (const int*)s->rlen[0].p};
+        CnsSeqs SB{(const unsigned char*)s->bps[1].p, (const long long*)s->boff[1].p, (const int*)s->rlen[1].p};
+        if (s->n_seg) {
+            if (pass == 0) {
+                ProfScope _ps(ctx, KID_CNS_COLUMNS);
+                hipLaunchKernelGGL(k_cns_columns, dim3((unsigned)((n_aln + CNS_BLOCK - 1) / CNS_BLOCK)), dim3(CNS_BLOCK), 0, ctx->stream, (const CnsAln*)s->alns.p, (int)n_aln,
+                                   (const CnsSeg*)s->segs.p, (const int*)s->indels.p, (const int*)s->n_indel.p, (const int*)s->n_ins.p, (int*)s->col_base.p, (CnsCols*)s->cols.p, 100);
+            }
+            if (tiled) {
+                const size_t lds = sizeof(unsigned) * 5 * ((size_t)tile + 1);
+                if (lds > 48 * 1024 && lds > s->vote_lds_attr) {
+                    CK(hipFuncSetAttribute((const void*)k_cns_vote_tiles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                    s->vote_lds_attr = lds;
+                }
+                ProfScope _ps(ctx, KID_CNS_VOTE);
+                const unsigned galn = (unsigned)((n_aln + CNS_BLOCK - 1) / CNS_BLOCK);
+                hipLaunchKernelGGL(k_cns_tile_count, dim3(galn), dim3(CNS_BLOCK), 0, ctx->stream, (const CnsAln*)s->alns.p, (int)n_aln, (const CnsSeg*)s->segs.p,
+                                   (const int*)s->tile_base.p, tile, (unsigned*)s->tile_ptr.p);
+                hipLaunchKernelGGL(k_cns_scan, dim3(1), dim3(1024), 0, ctx->stream, (unsigned*)s->tile_ptr.p, n_tiles + 1, total + 1);
+                CK(hipMemcpyAsync(s->tile_cursor.p, s->tile_ptr.p, sizeof(unsigned) * ((size_t)n_tiles + 1), hipMemcpyDeviceToDevice, ctx->stream));
+                hipLaunchKernelGGL(k_cns_tile_fill, dim3(galn), dim3(CNS_BLOCK), 0, ctx->stream, (const CnsAln*)s->alns.p, (int)n_aln, (const CnsSeg*)s->segs.p,
+                                   (const int*)s->tile_base.p, tile, (unsigned*)s->tile_cursor.p, (int*)s->seg_order.p);
+                hipLaunchKernelGGL(k_cns_vote_tiles, dim3((unsigned)n_tiles), dim3(CNS_BLOCK), lds, ctx->stream, SB, (const CnsAln*)s->alns.p, (const CnsSeg*)s->segs.p,
+                                   (const int*)s->indels.p, (const int*)s->n_indel.p, (const int*)s->col_base.p, (const CnsCols*)s->cols.p, (const long long*)s->cbase.p,
+                                   (const int*)s->tile_base.p, (const int*)s->contig_of_tile.p, (const unsigned*)s->tile_ptr.p, (const int*)s->seg_order.p, tile,
+                                   (int*)s->counts.p, (long long)plane, (int*)s->halo.p, (int*)s->scal.p);
+            } else {
+                ProfScope _ps(ctx, KID_CNS_VOTE);
+                hipLaunchKernelGGL(k_cns_vote, dim3((unsigned)((s->n_seg + CNS_BLOCK - 1) / CNS_BLOCK)), dim3(CNS_BLOCK), 0, ctx->stream, SB, (const CnsAln*)s->alns.p,
+                                   (const CnsSeg*)s->segs.p, (int)s->n_seg, (const int*)s->indels.p, (const int*)s->n_indel.p, (const int*)s->col_base.p, (const CnsCols*)s->cols.p,
+                                   (const long long*)s->cbase.p, (int*)s->counts.p, (long long)plane);
+            }
+        }
+        if (s->n_blocks) {
+            ProfScope _ps(ctx, KID_CNS_CALL);
+            hipLaunchKernelGGL(k_cns_call, dim3((unsigned)s->n_blocks), dim3(CNS_BLOCK), 0, ctx->stream, SA, (const int*)s->counts.p, (long long)plane, (long long)s->n_pos,
+                               (const int2*)s->contig_of_block.p, (const long long*)s->cbase.p, (unsigned*)s->packed.p, (unsigned*)s->block_sum.p, (CnsStats*)s->stats.p,
+                               (tiled && s->n_seg) ? (const int*)s->halo.p : (const int*)nullptr, (const int*)s->tile_base.p, tile);
+            hipLaunchKernelGGL(k_cns_scan, dim3(1), dim3(1024), 0, ctx->stream, (unsigned*)s->block_sum.p, s->n_blocks, total);
+            hipLaunchKernelGGL(k_cns_emit, dim3((unsigned)s->n_blocks), dim3(CNS_BLOCK), 0, ctx->stream, (const unsigned*)s->packed.p, (const int2*)s->contig_of_block.p,
+                               (const long long*)s->cbase.p, (const unsigned*)s->block_sum.p, (char*)s->out.p);
+        }
+        CK(hipGetLastError());
+        // results to the host: the strings, the block offsets (where a contig's string starts), statistics, chop offsets
+        CK(hipMemcpyAsync(scal_h, s->scal.p, 64, hipMemcpyDeviceToHost, ctx->stream));
+        s->h_block_off.assign((size_t)s->n_blocks + 1, 0);
+        if (s->n_blocks) CK(hipMemcpyAsync(s->h_block_off.data(), s->block_sum.p, sizeof(unsigned) * (size_t)s->n_blocks, hipMemcpyDeviceToHost, ctx->stream));
+        s->h_stats.assign((size_t)std::max(n_contigs, 1), CnsStats{});
+        if (n_contigs) CK(hipMemcpyAsync(s->h_stats.data(), s->stats.p, sizeof(CnsStats) * (size_t)n_contigs, hipMemcpyDeviceToHost, ctx->stream));
+        s->h_cols.assign((size_t)std::max<int64_t>(n_aln, 1), CnsCols{});
+        if (n_aln) CK(hipMemcpyAsync(s->h_cols.data(), s->cols.p, sizeof(CnsCols) * (size_t)n_aln, hipMemcpyDeviceToHost, ctx->stream));
+        CK(hipStreamSynchronize(ctx->stream));
+        if (!(tiled && ((int)(scal_h[0] & 0xffffffffu) & CNS_ST_VOTE16))) break;
+        tiled = false;
+    }
     const int st = (int)(scal_h[0] & 0xffffffffu);
     if (st & CNS_ST_WAVES) return fail(ctx, HINGE_E_RANGE, "hinge consensus: a trace-point segment needs more edit operations than its alignment's recorded diffs (the reference overruns its wave arrays here, LAInterface.cpp:3444-3466)");
     if (st & CNS_ST_INDELS) return fail(ctx, HINGE_E_RANGE, "hinge consensus: a segment's indel list outgrew its slots");

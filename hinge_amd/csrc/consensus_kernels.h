@@ -45,13 +45,17 @@ constexpr int CNS_ST_WAVES = 1;    // a segment needed more waves than its align
 constexpr int CNS_ST_INDELS = 2;   // ... or more indel slots
 constexpr int CNS_ST_RANGE = 4;    // a coordinate outside its sequence
 constexpr int CNS_ST_TRACE = 8;    // trace points inconsistent with the alignment's coordinates (k_cns_segments)
+constexpr int CNS_ST_VOTE16 = 16;  // k_cns_vote_tiles: a 16-bit inserted-base counter was about to wrap (the host votes again with k_cns_vote's int32 counters)
+constexpr int CNS_BPS_SPARE = 8;   // bytes the device copy of a .bps has behind its last byte (hinge_consensus_set_db): what cns_window may read there
 
 __device__ __forceinline__ int cns_base(const unsigned char* __restrict__ bps, long long boff, int p) {
     const unsigned b = bps[boff + (p >> 2)];
     return (int)((b >> (6 - 2 * (p & 3))) & 3u);
 }
 // 16 consecutive bases of a packed sequence as one word, the FIRST base in the top two bits: two aligned 32-bit loads around
-// the (byte-unaligned) start, composed big-endian.  Reads up to 8 bytes behind the last base's byte (the .bps copy has spare bytes).
+// the (byte-unaligned) start, composed big-endian.  x must be a base OF the sequence (x < its length): the loads then end at most
+// CNS_BPS_SPARE - 1 bytes behind the .bps' last byte, inside the spare bytes of the device copy.  A window that STARTS behind the
+// last base may not be loaded (it can lie up to 3 bytes behind the spare ones): cns_stage writes 0 for it.
 __device__ __forceinline__ unsigned cns_window(const unsigned char* __restrict__ bps, long long boff, int x) {
     const unsigned long long at = (unsigned long long)(bps + boff + (x >> 2));
     const unsigned* __restrict__ q = reinterpret_cast<const unsigned*>(at & ~3ull);
@@ -65,7 +69,8 @@ struct CnsPair {                   // the two sequences of one alignment, addres
     int comp, blen;
     __device__ __forceinline__ int A(int x) const { return cns_base(abps, aoff, x); }
     __device__ __forceinline__ int B(int x) const { return comp ? 3 - cns_base(bbps, boff, blen - 1 - x) : cns_base(bbps, boff, x); }
-    // bases x .. x + 15 of aseq / bseq, first base on top (what lies behind a sequence's end is whatever follows it in memory: callers bound their use)
+    // bases x .. x + 15 of aseq / bseq, first base on top; x < the sequence's length (cns_window).  What lies behind a sequence's end
+    // is whatever follows it in memory (the next sequence, the spare bytes): callers bound their use
     __device__ __forceinline__ unsigned winA(int x) const { return cns_window(abps, aoff, x); }
     __device__ __forceinline__ unsigned winB(int x) const {
         if (!comp) return cns_window(bbps, boff, x);
@@ -92,7 +97,7 @@ struct CnsWaves {
     int* W; int width, lo0;
     __device__ __forceinline__ int klo(int D) const { return lo0 - (D > 0 ? (D >> 1) : 0) - 1; }
     __device__ __forceinline__ int* at(int D, int k) const { return W + (((D + 2) * width + (k - klo(D))) << 6); }
-    __device__ __forceinline__ int* row(int D) const { return at(D, 0); }                   // row(D)[k << 6]
+    __device__ __forceinline__ int* row(int D) const { return at(D, 0); }                   // row(D)[k * 64]
     __device__ __forceinline__ int v(int D, int k) const { return *at(D, k) >> 8; }
     __device__ __forceinline__ int h(int D, int k) const { return (int)(signed char)(*at(D, k) & 0xff); }
     __device__ __forceinline__ void set_v(int D, int k, int val) { int* p = at(D, k); *p = (int)((unsigned)val << 8) | (*p & 0xff); }
@@ -118,6 +123,16 @@ __device__ __forceinline__ unsigned cns_lds_window(const unsigned* L, int x) {
     return (unsigned)((two << (2 * (x & 15))) >> 32);
 }
 __device__ __forceinline__ int cns_lds_base(const unsigned* L, int x) { return (int)((L[(x >> 4) * 256] >> (30 - 2 * (x & 15))) & 3u); }
+// The staging of one segment (m, n <= CNS_LDS_BASES): ceil(m / 16) windows per side and one word more, which cns_lds_window reads as
+// the second half of the last window and never uses a bit of.  That word would start at or behind the segment's end - behind the
+// sequence's end, and for the last sequence of a DB behind the .bps copy's spare bytes - so it is written as 0, not loaded.
+__device__ __forceinline__ void cns_stage(const CnsPair& S, int a0, int m, int b0, int n, unsigned* LA, unsigned* LB) {
+    const int na = (m + 15) / 16, nb = (n + 15) / 16;
+    for (int j = 0; j < na; j++) LA[j * 256] = S.winA(a0 + 16 * j);
+    LA[na * 256] = 0u;
+    for (int j = 0; j < nb; j++) LB[j * 256] = S.winB(b0 + 16 * j);
+    LB[nb * 256] = 0u;
+}
 
 __device__ inline int cns_iter_np(const CnsPair& S, int a0, int M, int b0, int N, CnsWaves w, int dcap, int* __restrict__ out, int out_cap, int& n_ins,
                                   const unsigned* LA = nullptr, const unsigned* LB = nullptr) {
@@ -126,7 +141,7 @@ __device__ inline int cns_iter_np(const CnsPair& S, int a0, int M, int b0, int N
     w.lo0 = low;
     {
         int* r2 = w.row(-2); int* r1 = w.row(-1);
-        for (int k = low - 1; k <= hgh + 1; k++) { r2[k << 6] = -512; r1[k << 6] = -512; }
+        for (int k = low - 1; k <= hgh + 1; k++) { r2[k * 64] = -512; r1[k * 64] = -512; }
         r1[0] = -256;
     }
     low += 1; hgh -= 1;
@@ -137,9 +152,9 @@ __device__ inline int cns_iter_np(const CnsPair& S, int a0, int M, int b0, int N
         int* __restrict__ F0 = w.row(D);
         const int* __restrict__ F1 = w.row(D - 1);
         const int* __restrict__ F2 = w.row(D - 2);
-        F0[(hgh + 1) << 6] = -512; F0[(low - 1) << 6] = -512;
+        F0[(hgh + 1) * 64] = -512; F0[(low - 1) * 64] = -512;
         auto move = [&](int k, int am, int ap, int mdir, int pdir) {
-            const int ac = (F1[k << 6] >> 8) + 1;
+            const int ac = (F1[k * 64] >> 8) + 1;
             int j, hc;
             if (ac < am) { if (ap < am) { hc = mdir; j = am; } else { hc = pdir; j = ap; } }
             else { if (ap < ac) { hc = 0; j = ac; } else { hc = pdir; j = ap; } }
@@ -155,14 +170,14 @@ __device__ inline int cns_iter_np(const CnsPair& S, int a0, int M, int b0, int N
                     j += eq < room ? eq : room;
                     if (eq < 16) break;
                 }
-            F0[k << 6] = (int)((unsigned)j << 8) | (hc & 0xff);
+            F0[k * 64] = (int)((unsigned)j << 8) | (hc & 0xff);
             return j;
         };
         int j = -2;
-        for (int k = hgh; k > del; k--) j = move(k, F2[(k - 1) << 6] >> 8, j + 1, -1, 4);
+        for (int k = hgh; k > del; k--) j = move(k, F2[(k - 1) * 64] >> 8, j + 1, -1, 4);
         j = -2;
-        for (int k = low; k < del; k++) j = move(k, j, (F2[(k + 1) << 6] >> 8) + 1, 2, 1);
-        j = move(del, j, (F0[(del + 1) << 6] >> 8) + 1, 2, 4);
+        for (int k = low; k < del; k++) j = move(k, j, (F2[(k + 1) * 64] >> 8) + 1, 2, 1);
+        j = move(del, j, (F0[(del + 1) * 64] >> 8) + 1, 2, 4);
         if (j >= N) break;
     }
     // trace-back with re-sliding (LAInterface.cpp:3285-3352)
@@ -246,11 +261,7 @@ __global__ __launch_bounds__(CNS_BLOCK) void k_cns_realign(CnsSeqs SA, CnsSeqs S
         int nins = 0;
         // the segment's bases to LDS (independent loads, issued together) unless it is longer than the staging area
         const bool staged = g.m <= CNS_LDS_BASES && g.n <= CNS_LDS_BASES;
-        if (staged) {
-            const int na = (g.m + 15) / 16 + 1, nb = (g.n + 15) / 16 + 1;
-            for (int j = 0; j < na; j++) LW[0][j][threadIdx.x] = S.winA(g.a0 + 16 * j);
-            for (int j = 0; j < nb; j++) LW[1][j][threadIdx.x] = S.winB(g.b0 + 16 * j);
-        }
+        if (staged) cns_stage(S, g.a0, g.m, g.b0, g.n, &LW[0][0][threadIdx.x], &LW[1][0][threadIdx.x]);
         const int cnt = cns_iter_np(S, g.a0, g.m, g.b0, g.n, w, dcap, indels + g.out_off, g.out_cap, nins,
                                     staged ? &LW[0][0][threadIdx.x] : (const unsigned*)nullptr, staged ? &LW[1][0][threadIdx.x] : (const unsigned*)nullptr);
         if (cnt < 0) { atomicOr(status, cnt == -1 ? CNS_ST_WAVES : CNS_ST_INDELS); n_indel[s] = 0; n_ins_out[s] = 0; continue; }
@@ -359,8 +370,12 @@ __global__ __launch_bounds__(CNS_BLOCK) void k_cns_vote(CnsSeqs SB, const CnsAln
 // tspace (computeTracePTS cuts there), so every vote of a segment lands in ITS tile - except an inserted base behind the
 // segment's last A base, whose position is the first one of the next tile: the halo slot, written to `halo` and added by
 // k_cns_call.  One workgroup per tile: the tile's segments (binned by k_cns_tile_count / k_cns_tile_fill) vote with LDS
-// atomics into 16|16-packed counters (a contig with 65 536+ voting alignments takes the global-atomics kernel above), then
-// the workgroup stores its tile's nine planes with plain, coalesced stores: no global atomic, no memset of the planes.
+// atomics into 16|16-packed counters, then the workgroup stores its tile's nine planes with plain, coalesced stores: no global
+// atomic, no memset of the planes.  What 16 bits hold: an alignment has ONE column per A position among the aligned ones, so
+// the five aligned counters stay below the number of voting alignments, and a contig with 65 536 or more of them takes the
+// global-atomics kernel above (the host's test).  The inserted-base counters have no such bound - consecutive inserted bases of
+// one alignment all vote at the same position - so their atomics return the old value, and a half that stands at 0xffff before its
+// increment sets CNS_ST_VOTE16: the host then zeroes the planes and votes with k_cns_vote.  (5-9 % of the votes are inserted bases.)
 __host__ __device__ inline int cns_tile_len(int tspace) { return tspace >= 2048 ? tspace : (2048 / tspace) * tspace; }
 constexpr int CNS_TILE_MAX = 4096;       // positions a tile may have (LDS: 5 words per position)
 
@@ -404,8 +419,8 @@ __global__ __launch_bounds__(CNS_BLOCK) void k_cns_vote_tiles(CnsSeqs SB, const 
                                                               const int* __restrict__ n_indel, const int* __restrict__ col_base, const CnsCols* __restrict__ cols,
                                                               const long long* __restrict__ cbase, const int* __restrict__ tile_base, const int* __restrict__ contig_of_tile,
                                                               const unsigned* __restrict__ tile_ptr, const int* __restrict__ order, int tile, int* __restrict__ counts,
-                                                              long long plane, int* __restrict__ halo) {
-    extern __shared__ unsigned cnt_lds[];            // [tile + 1][5]: A|C, G|T, '-', iA|iC, iG|iT (16 bits each)
+                                                              long long plane, int* __restrict__ halo, int* __restrict__ status) {
+    HIP_DYNAMIC_SHARED(unsigned, cnt_lds)            // [tile + 1][5]: A|C, G|T, '-', iA|iC, iG|iT (16 bits each)
     const int t = blockIdx.x;
     const int cg = contig_of_tile[t];
     const int p0 = (t - tile_base[cg]) * tile;       // first position of the tile in its contig
@@ -416,6 +431,7 @@ __global__ __launch_bounds__(CNS_BLOCK) void k_cns_vote_tiles(CnsSeqs SB, const 
     __syncthreads();
     const unsigned s_lo = tile_ptr[t], s_hi = tile_ptr[t + 1];
     const unsigned char* __restrict__ bbps = SB.bps;
+    bool wrapped = false;
     for (unsigned x = s_lo + threadIdx.x; x < s_hi; x += CNS_BLOCK) {
         const int s = order[x];
         const CnsSeg g = segs[s];
@@ -425,10 +441,12 @@ __global__ __launch_bounds__(CNS_BLOCK) void k_cns_vote_tiles(CnsSeqs SB, const 
         auto Bb = [&](int j1) { return al.comp ? 3 - cns_base(bbps, boff, al.blen - j1) : cns_base(bbps, boff, j1 - 1); };
         CnsPair SP;                                  // (only its B side is used: bseq[x] = Bb(x + 1))
         SP.abps = bbps; SP.aoff = 0; SP.bbps = bbps; SP.boff = boff; SP.comp = al.comp; SP.blen = al.blen;
-        auto vote = [&](int pos, int slot) {         // slot 0-3 aligned base, 4 '-', 5-8 inserted base
-            const int w = slot < 4 ? (slot >> 1) : slot == 4 ? 2 : 3 + ((slot - 5) >> 1);
-            const unsigned inc = (slot < 4 ? (slot & 1) : slot == 4 ? 0 : ((slot - 5) & 1)) ? 0x10000u : 1u;
-            atomicAdd(&cnt_lds[(pos - p0) * 5 + w], inc);
+        auto vote = [&](int pos, int slot) {         // slot 0-3 aligned base, 4 '-'
+            atomicAdd(&cnt_lds[(pos - p0) * 5 + (slot >> 1)], (slot & 1) ? 0x10000u : 1u);
+        };
+        auto vote_ins = [&](int pos, int b) {        // inserted base b: the half must not stand at 0xffff before the increment
+            const unsigned old = atomicAdd(&cnt_lds[(pos - p0) * 5 + 3 + (b >> 1)], (b & 1) ? 0x10000u : 1u);
+            wrapped |= ((b & 1) ? (old >> 16) : (old & 0xffffu)) == 0xffffu;
         };
         int col = col_base[s];
         if (col >= c.end || col + g.m + g.out_cap < c.start) continue;
@@ -445,12 +463,13 @@ __global__ __launch_bounds__(CNS_BLOCK) void k_cns_vote_tiles(CnsSeqs SB, const 
                 }
                 col += cnt;
             } else {
-                if (col >= c.start && col < c.end) vote(i - 1, kind == 1 ? 5 + Bb(j) : 4);
+                if (col >= c.start && col < c.end) { if (kind == 1) vote_ins(i - 1, Bb(j)); else vote(i - 1, 4); }
                 col += 1;
             }
             return col < c.end;
         });
     }
+    if (wrapped) atomicOr(status, CNS_ST_VOTE16);
     __syncthreads();
     int* __restrict__ out = counts + base + p0;
     for (int p = threadIdx.x; p < np; p += CNS_BLOCK) {

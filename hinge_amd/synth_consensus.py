@@ -39,6 +39,7 @@ class ConsensusSpec:
     empty_contigs: int = 0                 # contigs without any alignment (printed as they are, consensus.cpp:158-162)
     tspace: int = 100
     seed: int = 1
+    contig_lens: Tuple[int, ...] = ()      # when given: the contigs' lengths, one per contig (contig_len's draw is skipped)
 
 
 @dataclass
@@ -97,10 +98,11 @@ def generate(spec: ConsensusSpec) -> ConsensusData:
     contigs, reads = [], []
     recs, traces = [], []
     n_total = spec.n_contigs + spec.empty_contigs
+    assert not spec.contig_lens or len(spec.contig_lens) == n_total
     tdt = np.uint8 if spec.tspace <= 125 else np.dtype("<u2")      # trace values: one byte up to tspace 125, two beyond (align.h:64-69)
     tmax = 255 if spec.tspace <= 125 else 65535
     for c in range(n_total):
-        L = int(rng.integers(spec.contig_len[0], spec.contig_len[1] + 1))
+        L = int(spec.contig_lens[c]) if spec.contig_lens else int(rng.integers(spec.contig_len[0], spec.contig_len[1] + 1))
         draft = rng.integers(0, 4, size=L, dtype=np.uint8)
         contigs.append(draft)
         if c >= spec.n_contigs:
@@ -192,6 +194,15 @@ CONFIGS = {
     "cns_noisy": ConsensusSpec(n_contigs=2, contig_len=(8_000, 12_000), coverage=30.0, p_sub=0.05, p_ins=0.09, p_del=0.05, seed=13),
     "cns_clean": ConsensusSpec(n_contigs=2, contig_len=(6_000, 9_000), coverage=8.0, p_sub=0.0, p_ins=0.0, p_del=0.0, draft_errors_per_kb=3.0, p_carry=1.0, seed=14),
     "cns_twobyte": ConsensusSpec(n_contigs=2, contig_len=(7_000, 10_000), coverage=14.0, read_len=(900, 3_000), tspace=200, seed=16),
+    # edges of the kernels' geometry (tests/test_consensus_*.py): tile = a multiple of tspace up to 2048 positions, = tspace from there on
+    "cns_edge_t64": ConsensusSpec(n_contigs=3, contig_lens=(4096, 4097, 4095), coverage=20.0, read_len=(600, 1_800), p_sub=0.05, p_ins=0.09, p_del=0.05, flank_max=0,
+                                  tspace=64, seed=21),      # tile 2048 = 32 x 64: contigs of two tiles, one base more, one base less
+    "cns_edge_t125": ConsensusSpec(n_contigs=2, contig_len=(3_000, 5_000), coverage=12.0, read_len=(600, 1_800), tspace=125, seed=22),   # the last one-byte trace spacing: tile 2000
+    "cns_edge_t126": ConsensusSpec(n_contigs=2, contig_len=(3_000, 5_000), coverage=12.0, read_len=(600, 1_800), tspace=126, seed=23),   # the first two-byte one: tile 2016
+    "cns_edge_t176": ConsensusSpec(n_contigs=2, contig_len=(3_000, 5_000), coverage=12.0, read_len=(600, 1_800), tspace=176, seed=24),   # the longest segment k_cns_realign stages in LDS
+    "cns_edge_t177": ConsensusSpec(n_contigs=2, contig_len=(3_000, 5_000), coverage=12.0, read_len=(600, 1_800), tspace=177, seed=25),   # ... and the first it does not
+    "cns_edge_t2048": ConsensusSpec(n_contigs=2, contig_lens=(4096, 6145), coverage=30.0, low_cov_windows=0, read_len=(2_000, 7_000), tspace=2048, seed=26),  # tile = tspace: two tiles, and three and one base
+    "cns_edge_t2458": ConsensusSpec(n_contigs=1, contig_lens=(9000,), coverage=30.0, low_cov_windows=0, read_len=(2_000, 7_000), tspace=2458, seed=27),      # 5 * 4 * 2459 B of LDS counters: past 48 KiB
     "cns_midsize": ConsensusSpec(n_contigs=3, contig_len=(60_000, 90_000), coverage=22.0, read_len=(2_000, 9_000), p_sub=0.04, p_ins=0.07, p_del=0.04, seed=17, low_cov_windows=3),
     "cns_bench": ConsensusSpec(n_contigs=4, contig_len=(900_000, 1_300_000), coverage=30.0, read_len=(3_000, 11_000), seed=15, low_cov_windows=3),
 }

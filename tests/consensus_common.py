@@ -27,10 +27,19 @@ def make(name, wd, **over):
 
 
 def run_reference(wd, out="ref.fasta"):
-    """(fasta bytes, stdout bytes) of the reference's own program; None when it was never built."""
+    """(fasta bytes, stdout bytes) of the reference's own program; None when it was never built - and, with a warning, when it gives up
+    with "Out of memory (Enlarging DP vector)": computeTracePTS reads one value behind an alignment's trace (LAInterface.cpp:3454,
+    points[tlen] for an even tlen) into dmax, and sizes its wave vector from it in int arithmetic (:3457, enlarge_vector's int
+    argument).  With a trace spacing of about 1 700 and more, heap garbage above a few ten thousand there overflows the size, so
+    the same files pass in one run and fail in the next.  The golden digests (made by a run that passed) still pin such a set."""
     if not os.path.exists(REF_BIN):
         return None
-    r = subprocess.run([REF_BIN, "draft", "reads", "draft.reads.las", out, "nominal.ini"], cwd=wd, stdout=subprocess.PIPE, check=True)
+    r = subprocess.run([REF_BIN, "draft", "reads", "draft.reads.las", out, "nominal.ini"], cwd=wd, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    if r.returncode == 1 and b"Enlarging DP vector" in r.stderr:
+        import warnings
+        warnings.warn("the reference program overflowed its wave vector's size on %s (its read behind the trace): not compared live" % wd)
+        return None
+    assert r.returncode == 0, (r.returncode, r.stderr.decode()[-1000:])
     return open(os.path.join(wd, out), "rb").read(), r.stdout
 
 

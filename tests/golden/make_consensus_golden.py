@@ -18,7 +18,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 
-NAMES = ["cns_tiny", "cns_small", "cns_noisy", "cns_clean", "cns_twobyte", "cns_midsize"]
+NAMES = ["cns_tiny", "cns_small", "cns_noisy", "cns_clean", "cns_twobyte", "cns_midsize",
+         "cns_edge_t64", "cns_edge_t125", "cns_edge_t126", "cns_edge_t176", "cns_edge_t177", "cns_edge_t2048", "cns_edge_t2458"]
 
 
 def sha_bytes(b):
