@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HINGE_LIB") or os.path.join(_HERE, "lib", "libhinge_hip.so")   # HINGE_LIB: another build of the library (tools/ablate_k2.sh)
 
 HINGE_OK = 0
+SEED_MAX_PLACEMENTS_LIMIT = 8   # HINGE_SEED_MAX_PLACEMENTS_LIMIT
 HINGE_E_ARG, HINGE_E_DEVICE, HINGE_E_CAPACITY, HINGE_E_UNDEFINED, HINGE_E_RANGE = -1, -2, -3, -4, -5
 ERR_NAMES = {-1: "HINGE_E_ARG", -2: "HINGE_E_DEVICE", -3: "HINGE_E_CAPACITY", -4: "HINGE_E_UNDEFINED", -5: "HINGE_E_RANGE"}
 
@@ -117,6 +118,9 @@ SYMBOLS = [
     ("hinge_trace_refine", C.c_int, [_VP, C.c_int64, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), _VP, _VP, _VP]),
     ("hinge_trace_local", C.c_int, [_VP, C.c_int64, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), _VP, _VP, _VP]),
     ("hinge_trace_last_stats", C.c_int, [_VP, _VP]),
+    ("hinge_seed_run", C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_int64)]),
+    ("hinge_seed_db_reads", C.c_int, [_VP, C.POINTER(C.c_int64)]),
+    ("hinge_seed_last_stats", C.c_int, [_VP, _VP]),
     ("hinge_profile_report", C.c_int, [_VP, _VP, _VP]),
     ("hinge_timer_start", C.c_int, [_VP]),
     ("hinge_timer_stop_ms", C.c_int, [_VP, C.POINTER(C.c_float)]),
@@ -573,6 +577,38 @@ class Context:
         st = np.zeros(8, np.int64)
         self._ck(self.lib.hinge_trace_last_stats(self.h, _ptr(st)))
         return dict(zip(("batches", "scratch_bytes", "runs", "rounds", "widened", "dropped", "empty", "empty_widened"), [int(v) for v in st[:8]]))
+
+    def seed_run(self, read_ids=None, k: int = 0, step: int = 0, window: int = 0, max_occ: int = 0, list_: int = 0, max_placements: int = 0, min_hits: int = 0):
+        """hinge_seed_run (`hinge seed`): k-mer placements of the reads of Consensus(ctx, draft_db, read_db) on the draft.  0 = the
+        default (HINGE_SEED_*, else 15, 2, 256, 16, 2048, 1, 3).  read_ids None = all reads.  Returns (placements int64 [m, 7] = rows
+        of (aread, bread, comp, abpos, aepos, bbpos, bepos) as trace_local takes them, count int32 [m], diag int32 [m], n_placed
+        int32 [n], status int32 [n, 2] = per strand 0 OK, 1 NONE, 2 OVERFLOW) and leaves the call's figures in seed_stats()."""
+        if read_ids is None:
+            nr = C.c_int64(0)
+            self._ck(self.lib.hinge_seed_db_reads(self.h, C.byref(nr)))
+            n, ids = int(nr.value), None
+        else:
+            ids = np.ascontiguousarray(read_ids, dtype=np.int32)
+            n = int(ids.size)
+        cap = n * SEED_MAX_PLACEMENTS_LIMIT                                        # room for any max_placements: the defaults are the library's alone
+        out = np.zeros(max(cap, 1), dtype=CNS_ALN_DTYPE)
+        count = np.zeros(max(cap, 1), dtype=np.int32)
+        diag = np.zeros(max(cap, 1), dtype=np.int32)
+        n_placed = np.zeros(max(n, 1), dtype=np.int32)
+        status = np.zeros((max(n, 1), 2), dtype=np.int32)
+        params = np.asarray([k, step, window, max_occ, list_, max_placements, min_hits], dtype=np.int32)
+        m = C.c_int64(0)
+        self._ck(self.lib.hinge_seed_run(self.h, _ptr(params), n, _ptr(ids), cap, _ptr(out), _ptr(count), _ptr(diag), _ptr(n_placed), _ptr(status), C.byref(m)))
+        m = m.value
+        pl = np.stack([out[name][:m].astype(np.int64) for name in ("aread", "bread", "comp", "abpos", "aepos", "bbpos", "bepos")], axis=1) if m else np.zeros((0, 7), np.int64)
+        return pl, count[:m], diag[:m], n_placed[:n], status[:n]
+
+    def seed_stats(self) -> dict:
+        """Of the last seed_run: jobs, batches, index entries, codes dropped by max_occ, OVERFLOW jobs, reads without placement, and
+        the microseconds the index took (host build, upload)."""
+        st = np.zeros(8, np.int64)
+        self._ck(self.lib.hinge_seed_last_stats(self.h, _ptr(st)))
+        return dict(zip(("jobs", "batches", "entries", "dropped_codes", "overflow", "unplaced", "index_us"), [int(v) for v in st[:7]]))
 
     def profile_enable(self, max_launches: int):
         self._ck(self.lib.hinge_profile_enable(self.h, int(max_launches)))

@@ -6,6 +6,8 @@ struct CnsState {
     DevBuf bps[2], boff[2], rlen[2];
     int n_seq[2] = {0, 0};
     std::vector<int32_t> h_rlen[2];
+    std::vector<uint8_t> h_bps0;         // the draft's packed bases and offsets as given (hinge_seed_run builds its index from them)
+    std::vector<int64_t> h_boff0;
     DevBuf alns, segs, trace, aln_slots, indels, n_indel, n_ins, col_base, cols, scratch, counts, cbase, packed, block_sum, contig_of_block, stats, out, scal;
     DevBuf tile_base, contig_of_tile, tile_ptr, tile_cursor, seg_order, halo;   // the LDS-tile vote
     size_t vote_lds_attr = 0;
@@ -57,6 +59,12 @@ int hinge_consensus_set_db(hinge_ctx* ctx, int32_t which, int32_t n, const int32
     CK(hipStreamSynchronize(ctx->stream));
     s->n_seq[which] = n;
     s->h_rlen[which].assign(rlen, rlen + n);
+    if (which == 0) {
+        s->h_bps0.clear();
+        s->h_boff0.clear();
+        if (bps_bytes) s->h_bps0.assign(bps, bps + bps_bytes);
+        if (n) s->h_boff0.assign(boff, boff + n);
+    }
     s->ran = false;
     return HINGE_OK;
 }

@@ -2,8 +2,8 @@
 //                                [--ends given|refine|local] [--extend E] [--scores M,X] [--min-score S]`
 // Not a program of the reference: it stands where demo/ecoli_demo/run.sh:30-37 runs HPC.daligner + LAmerge on (draft, reads) to get
 // the draft-vs-reads .las WITH trace points that `hinge consensus` needs.  Input: placements as PAF, query = read, target =
-// contig (what `minimap2 draft.fasta reads.fasta` prints).  The base-level alignment between the given end points and its trace
-// points are computed behind the C ABI (hinge_trace_run, include/hinge_hip.h) on the GPU; this file reads the DBs and the PAF,
+// contig (what `hinge seed` writes and `minimap2 draft.fasta reads.fasta` prints).  The base-level alignment between the given
+// end points and its trace points are computed behind the C ABI (hinge_trace_run, include/hinge_hip.h) on the GPU; this file reads the DBs and the PAF,
 // resolves names, and writes the .las (align.h:98-110: the records `Read_Overlap` reads).
 // --ends given (the default): the PAF's end points are exact (hinge_trace_run).  --ends refine: they are approximate - every
 // placement is widened by up to E bases per side and the best-scoring stretch of its path is kept (hinge_trace_refine); the
@@ -18,7 +18,8 @@ using namespace hh;
 
 static void usage() {
     fprintf(stderr, "usage: paf2las <draft db> <read db> <paf> <out.las> [--band W] [--band-max W] [--tspace T] [--draft-names FASTA] [--read-names FASTA]\n"
-                    "               [--ends given|refine|local] [--extend E] [--scores M,X] [--min-score S]\n");
+                    "               [--ends given|refine|local] [--extend E] [--scores M,X] [--min-score S]\n"
+                    "       <paf>: placements with query = read, target = contig, e.g. from `hinge seed <draft db> <read db> <paf>` (then --ends local)\n");
 }
 
 // first word of every header of a FASTA file -> record index

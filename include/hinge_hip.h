@@ -488,6 +488,51 @@ int hinge_trace_local(hinge_ctx* ctx, int64_t n, const hinge_cns_alignment* plac
  * went on to 2 W because they were EMPTY (hinge_trace_local). */
 int hinge_trace_last_stats(hinge_ctx* ctx, int64_t* out);
 
+/* ---- hinge seed -------------------------------------------------------------------------------------------------------------
+ * k-mer placements of reads on the draft: "read r, strand s, contig c, about this diagonal", for hinge_trace_local to align.
+ * Not a program of the reference (its run script calls DALIGNER there).  Uses the two DBs of hinge_consensus_set_db.
+ *   index      (host, once per call) every k-mer of every contig of DB 0 at every position, none across two contigs, as
+ *              (code, gpos) sorted by both; code = 2 bits per base, the first base on top; gpos = position in the concatenated
+ *              contigs; a code with more than max_occ entries has none
+ *   job        one per (read, strand); B = the read in the strand's frame (comp as in hinge_cns_alignment), blen its length.
+ *              Sampled positions p = 0, s, 2 s, ... <= blen - k, s = the smallest multiple of step with at most `list`
+ *              positions.  Every entry of p's code is a hit (d, p, gpos), d = gpos - p + blen, enumerated by p then gpos; hits
+ *              beyond `list` are dropped in that order and the job is flagged OVERFLOW
+ *   window     hits sorted by (d, p); cnt[i] = elements j >= i with d[j] < d[i] + window; the best window is the largest cnt, of
+ *              equal ones the smallest i; its representative is element i + cnt[i] / 2
+ *   more       (max_placements > 1) the same among elements whose d is at least `window` away from every chosen
+ *              [d[i], d[i] + window): d <= lo - window or d >= lo + 2 window; cnt[] stays as it was.  Ends after max_placements
+ *              picks, at a best cnt below min_hits, or at one below half the first pick's (2 cnt < first)
+ *   placement  the WHOLE read along the representative's diagonal, clamped to the contig that holds gpos, both sequences cut by
+ *              the same amount; fewer than k bases left: none.  Flanks, chimeric tails and drift are hinge_trace_local's
+ *   per read   both strands' placements by cnt descending, forward before complement, d ascending; the first max_placements
+ * params: 0 = the default - HINGE_SEED_K / _STEP / _WINDOW / _MAX_OCC / _LIST / _MAX_PLACEMENTS / _MIN_HITS, else k 15 (8..16), step 2,
+ *   window 256 (a power of two, 16..65536), max_occ 16 (1..256), list 2048 (a power of two, 64..4096), max_placements 1 (1..8),
+ *   min_hits HINGE_SEED_MIN_HITS = 3: the largest best-window count of 16 unrelated reads of 7 128 random bases on a random
+ *   4.6 Mb draft, both strands, was 2; plus half, rounded up (tools/seed_measure.py min-hits).  NULL = all defaults.
+ * read_ids[n_reads], or NULL = all reads of DB 1 (n_reads is then -1 or their number: hinge_seed_db_reads).
+ * Outputs: out / count / diag [cap], cap >= n_reads x max_placements (HINGE_SEED_MAX_PLACEMENTS_LIMIT per read always suffices): the placements of the reads one after the other (tlen 0,
+ *   trace_off 0; what hinge_trace_local reads), a placement's cnt, and its diagonal gpos - p of the representative (= d - blen);
+ *   n_placed[n_reads]; status[2 n_reads] = per (read, strand) 0 OK, 1 NONE (read shorter than k, or no window of min_hits),
+ *   2 OVERFLOW (as OK, hits were dropped); *n_out = placements written.
+ * HINGE_E_ARG: parameters outside their range.  HINGE_E_RANGE: a read id outside DB 1.  HINGE_E_CAPACITY (before any launch): a
+ * draft of 2^31 or more bases, cap too small.  HINGE_E_DEVICE: a failed allocation, or an output slot the kernel did not write
+ * (the outputs are poisoned before every launch).  Jobs run in batches under HINGE_SEED_SCRATCH_MB (256) of job and result slots.
+ * Not claimed: chaining; a second stretch of one read on the same diagonal; hits from a repeat of more than max_occ copies;
+ * read-vs-read overlaps; more than one GPU.                                                                                   */
+typedef struct hinge_seed_params {
+    int32_t k, step, window, max_occ, list, max_placements, min_hits;
+} hinge_seed_params;
+#define HINGE_SEED_MIN_HITS 3
+#define HINGE_SEED_MAX_PLACEMENTS_LIMIT 8
+int hinge_seed_run(hinge_ctx* ctx, const hinge_seed_params* params, int64_t n_reads, const int32_t* read_ids, int64_t cap, hinge_cns_alignment* out, int32_t* count, int32_t* diag,
+                   int32_t* n_placed, int32_t* status, int64_t* n_out);
+/* The read count of DB 1 as hinge_consensus_set_db got it: what n_placed and status are sized by when read_ids is NULL. */
+int hinge_seed_db_reads(hinge_ctx* ctx, int64_t* n_reads);
+/* Of the last hinge_seed_run: out[0] jobs, [1] batches, [2] index entries, [3] codes dropped by max_occ, [4] OVERFLOW jobs, [5] reads
+ * without placement, [6] microseconds of the index (host build, upload), [7] 0. */
+int hinge_seed_last_stats(hinge_ctx* ctx, int64_t* out);
+
 /* Per-kernel timing with HIP events recorded around every launch on the context's stream.
  * enable(max_launches > 0) starts a fresh recording; report() synchronises and returns total ms and
  * launch count per kernel id in [0, hinge_profile_kernels()).  select() restricts the events to the
