@@ -55,6 +55,7 @@ SYMBOLS = [
     ("hinge_span16_pad", C.c_int, []),
     ("hinge_get_pileup_facts", C.c_int, [_VP, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     ("hinge_set_pile_bins", C.c_int, [_VP, C.c_int32, _VP, C.c_int]),
+    ("hinge_set_pile_cov", C.c_int, [_VP, C.c_int32, _VP, C.c_int]),
     ("hinge_attach_mask_table", C.c_int, [_VP, _VP]),
     ("hinge_attach_mean_cov", C.c_int, [_VP, _VP]),
     ("hinge_set_mask_rows", C.c_int, [_VP, C.c_int32, C.c_int32, _VP]),
@@ -267,6 +268,12 @@ class Context:
         """The per-read bin counts of the pile-ups just set (pile_bins()): the one-sweep pass then launches no k_cov_stats at all."""
         self._keep.append(nbins)
         self._ck(self.lib.hinge_set_pile_bins(self.h, int(reso), _ptr(nbins), 1 if on_device else 0))
+
+    def set_pile_cov(self, cov_sum, reso: int = 40, on_device: bool = False):
+        """The per-read sums of those profiles (pile_cov()), after set_pile_bins at the same reso: the library works out the part's
+        median coverage on the host and the pass starts with the exact MIN_COV (no k_spec_predict, k_median_hist or guard-band launch)."""
+        self._keep.append(cov_sum)
+        self._ck(self.lib.hinge_set_pile_cov(self.h, int(reso), _ptr(cov_sum), 1 if on_device else 0))
 
     def pileup_facts(self):
         """(largest pile-up, every span inside its read) of the current part."""
@@ -828,6 +835,25 @@ def pile_bins(row_ptr: np.ndarray, a_span: np.ndarray, rlen: np.ndarray, reso: i
     rl = np.asarray(rlen, dtype=np.int64)[:nr][has]
     ok = (rmn >= 0) & (rmx <= rl) & (counts[has] < 65536)
     out[has] = np.where(ok, rmx // reso + 2, -1).astype(np.int32)
+    return out
+
+
+def pile_cov(row_ptr: np.ndarray, a_span: np.ndarray, rlen: np.ndarray, reso: int = 40) -> np.ndarray:
+    """What an ingest hands to set_pile_cov: per read of the block the sum of its plain coverage profile, as int32.  With every
+    coordinate inside [0, rlen] the profile's events all fall inside its bins and the sum telescopes to the sum over the read's
+    overlaps of (aepos // reso - abpos // reso); 0 where pile_bins() says -1.  numpy restatement of LasPart::finish_facts."""
+    row_ptr = np.asarray(row_ptr, dtype=np.int64)
+    a_span = np.asarray(a_span, dtype=np.int32).reshape(-1, 2)
+    nr = len(row_ptr) - 1
+    out = np.zeros(nr, np.int32)
+    if a_span.shape[0] == 0 or int(row_ptr[-1]) == int(row_ptr[0]):
+        return out
+    lo, end = int(row_ptr[0]), int(row_ptr[-1])
+    ok = pile_bins(row_ptr, a_span, rlen, reso) >= 0
+    a = a_span[lo:end].astype(np.int64)
+    a = np.where(np.repeat(ok, np.diff(row_ptr))[:, None], a, 0)           # (coordinates of the other reads: not summed)
+    run = np.concatenate([[0], np.cumsum(a[:, 1] // reso - a[:, 0] // reso)])
+    out[:] = (run[row_ptr[1:] - lo] - run[row_ptr[:-1] - lo]).astype(np.int32)   # (int64 sums, stored as the kernels store them)
     return out
 
 

@@ -800,6 +800,63 @@ __global__ __launch_bounds__(SPEC_BLOCK) void k_spec_predict(SpecBatch B, int re
 }
 
 // ------------------------------------------------------------------------------------------------
+// Exact-first pass, step 1 (instead of k_spec_predict, k_median_hist and the guard-band launch): the ingest handed over every
+// read's coverage sum (hinge_set_pile_cov), so the part's median, n_long and totals were worked out on the host when the sums
+// were set and MIN_COV is exact BEFORE the sweep.  Workgroup 0 of a part clears the pass scalars - the totals and the status
+// among them get their values in the same store - applies a pending MIN_COV and performs filter.cpp:671-678 on the device,
+// against the running value (a context that sees several parts carries the maximum over).  All workgroups of a part write
+// the means (filter.cpp:642-656) where the table does not hold them yet (mean_out == nullptr: it does; no such workgroups).
+// No workgroup depends on another: no ticket.  Up to MED_BATCH_MAX parts per launch (workgroup b works for part b % n).
+// ------------------------------------------------------------------------------------------------
+struct ExactPart {
+    int r_begin, r_end;
+    int* pass_scalars; int n_pass_scalars, totals_at, status_at;   // (indices of totals[0..1] (64-bit) and status in pass_scalars)
+    int* min_cov; int set_min_cov, min_cov_value;
+    int* spec_min_cov;            // hinge_filter_spec_stats: "predicted" = exact
+    int* est;
+    int cov_est, n_long;          // rank n/2 of the valid means, their number (0: no read >= 5000 bp - ST_NO_LONG_READ, MIN_COV stays)
+    long long total_cov, num_slot;
+    const int* cov_tot; const int* nbins0; const int* rlen; int* mean_out;
+};
+struct ExactBatch {
+    ExactPart part[MED_BATCH_MAX];
+    int n;
+};
+__global__ __launch_bounds__(256) void k_exact_begin(ExactBatch B, int est_cov_override) {
+    const unsigned n_parts = (unsigned)B.n;
+    const ExactPart& A = B.part[blockIdx.x % n_parts];
+    const unsigned bx = blockIdx.x / n_parts, gx = gridDim.x / n_parts;
+    if (bx >= gx) return;
+    const int tid = threadIdx.x;
+    if (bx == 0) {
+        for (int t = tid; t < A.n_pass_scalars; t += 256) {
+            int v = 0;
+            if (t == A.totals_at) v = (int)(unsigned)((unsigned long long)A.total_cov & 0xffffffffull);
+            else if (t == A.totals_at + 1) v = (int)(unsigned)((unsigned long long)A.total_cov >> 32);
+            else if (t == A.totals_at + 2) v = (int)(unsigned)((unsigned long long)A.num_slot & 0xffffffffull);
+            else if (t == A.totals_at + 3) v = (int)(unsigned)((unsigned long long)A.num_slot >> 32);
+            else if (t == A.status_at) v = A.n_long == 0 ? ST_NO_LONG_READ : 0;
+            A.pass_scalars[t] = v;
+        }
+        if (tid == 0) {
+            int mc = A.set_min_cov ? A.min_cov_value : *A.min_cov;   // (nobody else writes *min_cov in this launch)
+            A.est[0] = A.n_long ? A.cov_est : 0;
+            A.est[1] = A.n_long;
+            if (A.n_long) {
+                const int cov_est = est_cov_override != 0 ? est_cov_override : A.cov_est;   // filter.cpp:671
+                mc = max(mc, cov_est / 3);                                                   // filter.cpp:677-678
+            }
+            *A.min_cov = mc;
+            *A.spec_min_cov = mc;
+        }
+    }
+    if (A.mean_out) {
+        for (long long i = (long long)A.r_begin + bx * 256u + tid; i <= A.r_end; i += (long long)gx * 256)
+            A.mean_out[i] = fused_mean(A.nbins0[i], A.cov_tot[i], A.rlen[i], A.mean_out[i]);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Facts about a part's pile-ups that stay true for every pass over it (run once by hinge_set_pileups):
 // facts[0] = largest pile-up, facts[1] = 1 if some coordinate lies outside [0, rlen].  With them the host
 // knows when the hand-back launch of K2 and the serial exact-path kernel of K3 cannot have work.

@@ -10,6 +10,7 @@
 #include <vector>
 #include "../../include/hinge_hip.h"
 #include "filter_kernels.h"
+#include "pile_cov_host.h"
 #include "filter_long_kernels.h"
 #include "hinge_call_kernel.h"
 #include "align_kernels.h"
@@ -50,6 +51,15 @@ struct hinge_ctx {
     bool mean_attached = false;
     DevBuf cmask, rflags, nbins0, keep;
     int nbins0_reso = -1;               // reso k_cov_stats last filled nbins0[] at for the current pile-ups (-1: not yet)
+    // the exact-first pass (hinge_set_pile_cov): the ingest's per-read coverage sums are in cov_tot[] and what the median kernel
+    // would make of them was worked out on the host when they were set
+    std::vector<int32_t> h_nbins0;      // host copy of the bins hinge_set_pile_bins was given (reads r_begin .. r_end)
+    int cov_reso = -1;                  // reso of the sums (-1: none; dropped with the pile-ups, like nbins0_reso)
+    PileCovEstimate cov_host;           // eligible, cov_est, n_long, total_cov, num_slot of the current part
+    bool mean_current = false;          // mean_cov[r_begin .. r_end] holds the means of these sums (k_exact_begin wrote them)
+    bool pass_exact = false;            // the current pass's sweep ran with the exact MIN_COV: finish_batch has nothing to do
+    bool spec_debugged = false;         // hinge_debug_spec was called: the context stays on the speculative pass
+    int ingest_cov = 1;                 // HINGE_INGEST_COV=0: the sums are not used (the speculative pass, for A/B runs)
     DevBuf span16;             // 16|16-bit copy of a_span (abpos | aepos << 16) for the two streaming kernels
     bool use_span16 = false;   // every read < 65536 bp and every coordinate inside its read (k_pileup_facts)
     int no_span16 = 0;         // HINGE_NO_SPAN16=1: keep the streaming kernels on the int32 spans
@@ -158,10 +168,10 @@ struct hinge_ctx {
 };
 
 enum KernelId { KID_STATS = 0, KID_MEDIAN, KID_MASK_ANNOTATE, KID_MASK_FALLBACK, KID_HINGE_COUNT, KID_HINGE_CALL, KID_HINGE_EXACT, KID_COVERAGE_BINS, KID_TRIM_CLASSIFY,
-                KID_PILEUP_FACTS, KID_MATCHING_POSITION, KID_SELECT_EDGES, KID_SPEC_PREDICT, KID_MASK_FINAL, KID_CNS_REALIGN, KID_CNS_COLUMNS, KID_CNS_VOTE, KID_CNS_CALL, KID_DRAFT_ALIGN, KID_DRAFT_CNS, KID_DRAFT_ALIGN_LONG, KID_DRAFT_CNS_DEEP, KID_MASK_LONG, KID_TRACE_FILL, KID_TRACE_WALK, KID_TRACE_CLIP, KID_TRACE_FILL_LOCAL, KID_TRACE_WALK_LOCAL, KID_SEED_VOTE, KID_COUNT };
+                KID_PILEUP_FACTS, KID_MATCHING_POSITION, KID_SELECT_EDGES, KID_SPEC_PREDICT, KID_MASK_FINAL, KID_CNS_REALIGN, KID_CNS_COLUMNS, KID_CNS_VOTE, KID_CNS_CALL, KID_DRAFT_ALIGN, KID_DRAFT_CNS, KID_DRAFT_ALIGN_LONG, KID_DRAFT_CNS_DEEP, KID_MASK_LONG, KID_TRACE_FILL, KID_TRACE_WALK, KID_TRACE_CLIP, KID_TRACE_FILL_LOCAL, KID_TRACE_WALK_LOCAL, KID_SEED_VOTE, KID_EXACT_BEGIN, KID_COUNT };
 static const char* const KERNEL_NAMES[KID_COUNT] = {"k_cov_stats", "k_median_hist", "k_mask_annotate", "k_mask_annotate_fallback", "k_hinge_count", "k_hinge_call", "k_hinge_exact",
                                                      "k_coverage_bins", "k_trim_classify", "k_pileup_facts", "k_matching_position", "k_select_edges", "k_spec_predict",
-                                                     "k_mask_annotate_final", "k_cns_realign", "k_cns_columns", "k_cns_vote", "k_cns_call", "k_draft_align", "k_draft_cns", "k_draft_align_long", "k_draft_cns_deep", "k_mask_annotate_long", "k_trace_fill", "k_trace_walk", "k_trace_clip", "k_trace_fill_local", "k_trace_walk_local", "k_seed_vote"};
+                                                     "k_mask_annotate_final", "k_cns_realign", "k_cns_columns", "k_cns_vote", "k_cns_call", "k_draft_align", "k_draft_cns", "k_draft_align_long", "k_draft_cns_deep", "k_mask_annotate_long", "k_trace_fill", "k_trace_walk", "k_trace_clip", "k_trace_fill_local", "k_trace_walk_local", "k_seed_vote", "k_exact_begin"};
 
 struct ProfScope {
     hinge_ctx* c;
@@ -312,6 +322,7 @@ int hinge_ctx_create(int device, hinge_ctx** out) {
     if (const char* g = getenv("HINGE_DEBUG_FORCE_EXACT")) ctx->force_exact = atoi(g);   // 1: serial exact kernel, 2: exact replay in LDS (tests)
     ctx->debug_paths = getenv("HINGE_DEBUG_PATHS") != nullptr;
     if (const char* g = getenv("HINGE_ONE_SWEEP")) ctx->one_sweep = atoi(g);
+    if (const char* g = getenv("HINGE_INGEST_COV")) ctx->ingest_cov = atoi(g);
     if (const char* g = getenv("HINGE_FINAL_BATCH")) ctx->final_batched = atoi(g);
     if (const char* g = getenv("HINGE_K2_BATCH")) ctx->k2_batch = atoi(g);
     if (const char* g = getenv("HINGE_CALL_LIGHT")) ctx->hinge_light = atoi(g);
@@ -389,6 +400,8 @@ int hinge_set_reads(hinge_ctx* ctx, int32_t n_reads, const int32_t* rlen, const 
     ctx->cov_valid = false;
     ctx->long_key[0] = ctx->long_key[1] = ctx->long_key[2] = ctx->long_key[3] = -1;   // (so was the list of the long reads)
     ctx->n_long = 0;
+    ctx->cov_reso = -1;           // (the ingest's sums were judged with the old lengths, and cov_tot may move)
+    ctx->mean_current = false;
     size_t n = (size_t)n_reads;
     if ((rc = ensure(ctx, ctx->mask_own, sizeof(int2) * n))) return rc;
     if ((rc = ensure(ctx, ctx->mean_own, sizeof(int) * n))) return rc;
@@ -445,6 +458,10 @@ static int set_pileups_impl(hinge_ctx* ctx, int32_t r_begin, int32_t r_end, int6
     ctx->image_set = false;   // (a .las image belongs to the pile-ups it was set for)
     ctx->bspan16_state = 0;
     ctx->nbins0_reso = -1;
+    ctx->h_nbins0.clear();
+    ctx->cov_reso = -1;
+    ctx->mean_current = false;
+    ctx->pass_exact = false;
     ctx->cov_valid = false;
     int rc;
     if ((rc = adopt(ctx, ctx->row_ptr, row_ptr, sizeof(int64_t) * ((size_t)ctx->n_reads + 1), on_device))) return rc;
@@ -581,6 +598,7 @@ int hinge_attach_mean_cov(hinge_ctx* ctx, int32_t* d) {
     if (!ctx) return HINGE_E_ARG;
     ctx->mean_cov = d ? d : (int*)ctx->mean_own.p;
     ctx->mean_attached = d != nullptr;
+    ctx->mean_current = false;
     return HINGE_OK;
 }
 int hinge_device_count(void) {
@@ -604,6 +622,33 @@ int hinge_set_pile_bins(hinge_ctx* ctx, int32_t reso, const int32_t* nbins, int 
     CK(hipMemcpyAsync((int*)ctx->nbins0.p + ctx->r_begin, nbins, sizeof(int) * nr, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
     if (!on_device) CK(hipStreamSynchronize(ctx->stream));
     ctx->nbins0_reso = reso;
+    if (!on_device) ctx->h_nbins0.assign(nbins, nbins + nr);
+    else ctx->h_nbins0.clear();
+    ctx->cov_reso = -1;   // (sums belong to the bins they were set behind)
+    return HINGE_OK;
+}
+
+int hinge_set_pile_cov(hinge_ctx* ctx, int32_t reso, const int32_t* cov_sum, int on_device) {
+    if (!ctx || reso <= 0 || !cov_sum || ctx->r_end < ctx->r_begin || !ctx->cov_tot.p) return fail(ctx, HINGE_E_ARG, "hinge_set_pile_cov: bad arguments (call hinge_set_pileups first)");
+    if (ctx->nbins0_reso != reso) return fail(ctx, HINGE_E_ARG, "hinge_set_pile_cov: call hinge_set_pile_bins at the same reso first");
+    CK(hipSetDevice(ctx->device));
+    const size_t nr = (size_t)(ctx->r_end - ctx->r_begin + 1);
+    CK(hipMemcpyAsync((int*)ctx->cov_tot.p + ctx->r_begin, cov_sum, sizeof(int) * nr, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    // the host's view of the two arrays: fetched once, here, when they live on the device
+    std::vector<int32_t> h_cov;
+    if (on_device) {
+        h_cov.resize(nr);
+        CK(hipMemcpyAsync(h_cov.data(), cov_sum, sizeof(int) * nr, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (ctx->h_nbins0.size() != nr) {
+        ctx->h_nbins0.resize(nr);
+        CK(hipMemcpyAsync(ctx->h_nbins0.data(), (const int*)ctx->nbins0.p + ctx->r_begin, sizeof(int) * nr, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    CK(hipStreamSynchronize(ctx->stream));
+    if (ctx->h_rlen.size() < (size_t)ctx->r_end + 1) return fail(ctx, HINGE_E_ARG, "hinge_set_pile_cov: call hinge_set_reads first");
+    ctx->cov_host = pile_cov_estimate(ctx->h_rlen.data() + ctx->r_begin, ctx->h_nbins0.data(), on_device ? h_cov.data() : cov_sum, nr);
+    ctx->cov_reso = reso;
+    ctx->mean_current = false;
     return HINGE_OK;
 }
 
@@ -810,6 +855,8 @@ static int launch_stats(hinge_ctx* ctx, const hinge_filter_params* p) {
     CK(hipGetLastError());
     ctx->nbins0_reso = p->reso;   // nbins0[] now describes these pile-ups at this reso
     ctx->pass_mode = 0;           // a two-sweep pass: MIN_COV is exact when K2 starts
+    ctx->pass_exact = false;      // ... and K2 is still to come
+    ctx->mean_current = false;    // (the kernel stored the means itself, also where the ingest's sums do not define them)
     return HINGE_OK;
 }
 
@@ -1916,6 +1963,47 @@ static int launch_spec_predict(hinge_ctx** ctxs, int n, const hinge_filter_param
     return HINGE_OK;
 }
 
+// The exact-first pass (hinge_set_pile_cov): every part of the batch came with the ingest's coverage sums, so MIN_COV is known
+// before the sweep - k_exact_begin, then K2 in its exact instance; no prediction, no guard band, no verification, no final launch.
+static bool exact_first_applies(hinge_ctx* const* ctxs, int n, const hinge_filter_params* p, const uint32_t* hist_dev) {
+    if (hist_dev || p->reso != 40 || p->delete_telomere != 0) return false;
+    for (int k = 0; k < n; k++) {
+        const hinge_ctx* c = ctxs[k];
+        if (c->ingest_cov == 0 || c->one_sweep == 0 || c->spec_debugged || c->cov_reso != 40 || c->nbins0_reso != 40 || !c->cov_host.eligible) return false;
+    }
+    return true;
+}
+static int launch_exact_begin(hinge_ctx** ctxs, int n, const hinge_filter_params* p) {
+    hinge_ctx* ctx = ctxs[0];
+    static_assert(SCALARS_RESET_BYTES % sizeof(int) == 0, "reset region is whole ints");
+    static_assert(offsetof(Scalars, totals) % sizeof(int) == 0 && offsetof(Scalars, status) < SCALARS_RESET_BYTES, "totals and status are pass scalars");
+    ExactBatch B;
+    memset(&B, 0, sizeof(B));
+    B.n = n;
+    int max_nr = 0;
+    for (int k = 0; k < n; k++) {
+        hinge_ctx* c = ctxs[k];
+        ExactPart& a = B.part[k];
+        a.r_begin = c->r_begin; a.r_end = c->r_end;
+        a.pass_scalars = (int*)c->scalars.p; a.n_pass_scalars = (int)(SCALARS_RESET_BYTES / sizeof(int));
+        a.totals_at = (int)(offsetof(Scalars, totals) / sizeof(int)); a.status_at = (int)(offsetof(Scalars, status) / sizeof(int));
+        a.min_cov = &sc(c)->min_cov; a.set_min_cov = c->min_cov_pending ? 1 : 0; a.min_cov_value = c->min_cov_value;
+        c->min_cov_pending = false;
+        a.spec_min_cov = &sc(c)->spec_min_cov; a.est = sc(c)->est;
+        a.cov_est = c->cov_host.cov_est; a.n_long = c->cov_host.n_long; a.total_cov = c->cov_host.total_cov; a.num_slot = c->cov_host.num_slot;
+        a.cov_tot = (const int*)c->cov_tot.p; a.nbins0 = (const int*)c->nbins0.p; a.rlen = (const int*)c->rlen.p;
+        a.mean_out = c->mean_current ? nullptr : c->mean_cov;
+        if (!c->mean_current) max_nr = std::max(max_nr, c->r_end - c->r_begin + 1);
+        c->mean_current = true;
+        c->pass_mode = 0; c->n_wave_totals = 0; c->pass_exact = true;
+    }
+    const int bpp = std::max(1, std::min((max_nr + 1023) / 1024, 64));   // workgroups per part: four reads per thread where the means are due
+    ProfScope _ps(ctx, KID_EXACT_BEGIN);
+    hipLaunchKernelGGL(k_exact_begin, dim3(bpp * n), dim3(256), 0, ctx->stream, B, p->est_cov);
+    CK(hipGetLastError());
+    return HINGE_OK;
+}
+
 int hinge_filter_sweep_batch_async(hinge_ctx** ctxs, int32_t n, const hinge_filter_params* p, uint32_t* hist_dev, int64_t row_stride) {
     int rc = same_device_and_stream(ctxs, n, MED_BATCH_MAX, "hinge_filter_sweep_batch_async");
     if (rc) return rc;
@@ -1930,6 +2018,12 @@ int hinge_filter_sweep_batch_async(hinge_ctx** ctxs, int32_t n, const hinge_filt
     for (int k = 0; k < n; k++) { lo[k] = ctxs[k]->r_begin; hi[k] = ctxs[k]->r_end; hd[k] = hist_dev ? hist_dev + (int64_t)k * row_stride : nullptr; }
     // the telomere test (filter.cpp:731-760) sums max(cov, MIN_COV): not constant over a band of MIN_COV values - two sweeps
     const bool one_sweep = ctx->one_sweep != 0 && p->delete_telomere == 0;
+    for (int k = 0; k < n; k++) ctxs[k]->pass_exact = false;
+    if (one_sweep && exact_first_applies(ctxs, n, p, hist_dev)) {
+        if ((rc = launch_exact_begin(ctxs, n, p))) return rc;
+        return launch_mask_annotate_parts(ctxs, n, p, MODE_CLASSIC);
+    }
+    for (int k = 0; k < n; k++) ctxs[k]->mean_current = false;   // (the passes below store the means themselves)
     if (!one_sweep) {
         for (int k = 0; k < n; k++)
             if ((rc = launch_stats(ctxs[k], p))) return rc;
@@ -1948,11 +2042,14 @@ int hinge_filter_finish_batch_async(hinge_ctx** ctxs, int32_t n, const hinge_fil
     hinge_ctx* ctx = ctxs[0];
     if ((rc = check_params(ctx, p))) return rc;
     CK(hipSetDevice(ctx->device));
-    bool all_final = true;
-    for (int k = 0; k < n; k++) all_final = all_final && ctxs[k]->pass_mode != 0;
+    bool all_final = true, all_exact = true;
+    for (int k = 0; k < n; k++) { all_final = all_final && ctxs[k]->pass_mode != 0; all_exact = all_exact && ctxs[k]->pass_exact; }
+    if (all_exact) return HINGE_OK;   // the exact-first pass: the sweep was the whole mask / annotation pass
     if (!all_final || ctx->final_batched == 0) {
-        for (int k = 0; k < n; k++)
+        for (int k = 0; k < n; k++) {
+            if (ctxs[k]->pass_exact) continue;
             if ((rc = launch_mask_annotate(ctxs[k], p, ctxs[k]->pass_mode != 0 ? MODE_FINAL : MODE_CLASSIC))) return rc;
+        }
         return HINGE_OK;
     }
     // the guard-band lists of all parts in one launch per MASK_FINAL_BATCH_MAX parts (k_mask_final_batch)
@@ -2031,7 +2128,7 @@ int hinge_filter_spec_stats(hinge_ctx* ctx, int64_t out[6]) {
     CK(hipMemcpyAsync(&h, ctx->scalars.p, sizeof(Scalars), hipMemcpyDeviceToHost, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
     out[0] = h.spec_stats[0]; out[1] = h.spec_stats[1]; out[2] = h.spec_stats[2];
-    out[3] = ctx->pass_mode != 0 ? (int64_t)h.redo_count : -1;
+    out[3] = ctx->pass_mode != 0 ? (int64_t)h.redo_count : (ctx->pass_exact ? 0 : -1);   // (exact-first: no guard band, [4] == [5], [0..2] stand still)
     out[4] = h.spec_min_cov; out[5] = h.min_cov;
     return HINGE_OK;
 }
@@ -2041,6 +2138,7 @@ int hinge_debug_spec(hinge_ctx* ctx, int band, int sample, int bias) {
     if (band >= 0) ctx->spec_band = band;
     if (sample > 0) ctx->spec_ns = sample;
     ctx->spec_bias = bias;
+    ctx->spec_debugged = true;   // (what it sets only exists in the speculative pass: the context stays on it)
     return HINGE_OK;
 }
 

@@ -582,12 +582,14 @@ def resident_batch(parts, params, device: torch.device, gather_groups: int = 1, 
         span16, max_pile, in_range = capi.pack_spans(rp.row_ptr, rp.a_span, rp.rlen)
         bins = np.zeros(S, np.int32)                                   # (ids behind the block's reads: empty pile-ups)
         bins[:rp.n_reads] = capi.pile_bins(rp.row_ptr, rp.a_span, rp.rlen, int(params.reso))
+        sums = np.zeros(S, np.int32)                                   # ... and the sums of the reads' plain profiles
+        sums[:rp.n_reads] = capi.pile_cov(rp.row_ptr, rp.a_span, rp.rlen, int(params.reso))
         tens = (torch.from_numpy(row_ptr).to(device), torch.from_numpy(np.ascontiguousarray(rp.a_span, dtype=np.int32)).to(device),
                 torch.from_numpy(np.ascontiguousarray(rp.b_span, dtype=np.int32)).to(device), torch.from_numpy(b_flag.view(np.int32)).to(device),
                 None if span16 is None else torch.from_numpy(span16.view(np.int32)).to(device))
         ctx = capi.Context(device.index or 0)
         backend = HipBackend(ctx, params, rlen_t.cpu().numpy(), None, lo, lo + S - 1, tens[0], tens[1], tens[2], tens[3], span16=tens[4],
-                             facts=(max_pile, in_range), last_a=lo + rp.last_a, coverage_out=True, pile_bins=bins)
+                             facts=(max_pile, in_range), last_a=lo + rp.last_a, coverage_out=True, pile_bins=bins, pile_cov=sums)
         batch.set_backend(p, backend)
         ctxs.append(ctx)
     if batch.max_pileup() >= 4096:
@@ -601,7 +603,7 @@ class HipBackend:
     def __init__(self, ctx, params, rlen: np.ndarray, qv_mask: Optional[np.ndarray], r_begin: int, r_end: int,
                  row_ptr: torch.Tensor, a_span: torch.Tensor, b_span: torch.Tensor, b_flag: torch.Tensor,
                  span16: Optional[torch.Tensor] = None, facts: Optional[Tuple[int, bool]] = None, last_a: Optional[int] = None,
-                 coverage_out: bool = False, pile_bins: Optional[np.ndarray] = None):
+                 coverage_out: bool = False, pile_bins: Optional[np.ndarray] = None, pile_cov: Optional[np.ndarray] = None):
         """row_ptr ... b_flag: device tensors (adopted).  facts = (max_pile, spans_in_range) and span16 (device uint32/int32
         [n_ovl + capi.span16_pad()], or None) as the ingest produced them (capi.pack_spans): without facts the library sweeps the
         spans itself (k_pileup_facts).  last_a: A read of the part's last .las record (default r_end)."""
@@ -621,6 +623,8 @@ class HipBackend:
             ctx.set_pileups_packed(r_begin, r_end, row_ptr, a_span, b_span, b_flag, span16, facts[0], facts[1], n_ovl=int(b_flag.shape[0]), on_device=True)
         if pile_bins is not None:     # the ingest's per-read bin counts (capi.pile_bins): no device sweep before the one-sweep pass
             ctx.set_pile_bins(np.ascontiguousarray(pile_bins, dtype=np.int32), int(params.reso))
+            if pile_cov is not None:  # ... and their sums (capi.pile_cov): the part's median is known before the sweep (exact-first pass)
+                ctx.set_pile_cov(np.ascontiguousarray(pile_cov, dtype=np.int32), int(params.reso))
         ctx.coverage_out(coverage_out)
         ctx.set_min_cov(self.ini_min_cov)
 

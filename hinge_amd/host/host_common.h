@@ -570,13 +570,19 @@ struct LasPart {
     // ... and the bins of every read's plain coverage profile at reso 40 (hinge_set_pile_bins): 0 for an empty pile-up, else
     // max(abpos, aepos) / 40 + 2 over its overlaps, -1 for a coordinate outside [0, rlen] or 65 536+ overlaps
     std::vector<int32_t> nbins40;              // reads r_begin .. r_end
+    // ... and the sum of that profile (hinge_set_pile_cov): with every coordinate inside [0, rlen] the profile's begin and end
+    // events all fall inside its bins, so its sum telescopes to sum over the overlaps of (aepos / 40 - abpos / 40); 0 where
+    // nbins40 is -1 (the general kernel defines that read's sum)
+    std::vector<int32_t> cov40;                // reads r_begin .. r_end
     void finish_facts(int n_reads, const std::vector<int32_t>* rlen = nullptr) {
         int64_t mp = 0;
         for (int q = 0; q < n_reads; q++) mp = std::max(mp, row_ptr[(size_t)q + 1] - row_ptr[(size_t)q]);
         max_pile = (uint32_t)std::min<int64_t>(mp, 0x7fffffff);
         nbins40.clear();
+        cov40.clear();
         if (!rlen || r_end < r_begin || r_end >= n_reads) return;
         nbins40.assign((size_t)(r_end - r_begin + 1), 0);
+        cov40.assign(nbins40.size(), 0);
         parallel_dynamic((int64_t)nbins40.size(), 512, [&](int64_t k0, int64_t k1) {
             for (int64_t k = k0; k < k1; k++) {
                 const int q = r_begin + (int)k;
@@ -584,13 +590,16 @@ struct LasPart {
                 if (e == s) continue;
                 const uint32_t rl = (uint32_t)std::max((*rlen)[(size_t)q], 0);
                 int32_t mx = 0;
+                int64_t sum = 0;
                 bool ok = e - s < 65536;
                 for (int64_t t = s; t < e; t++) {
                     const int32_t ab = a_span[(size_t)(2 * t)], ae = a_span[(size_t)(2 * t + 1)];
                     ok = ok && (uint32_t)ab <= rl && (uint32_t)ae <= rl;
                     mx = std::max(mx, std::max(ab, ae));
+                    sum += ae / 40 - ab / 40;
                 }
                 nbins40[(size_t)k] = ok ? mx / 40 + 2 : -1;
+                cov40[(size_t)k] = ok ? (int32_t)sum : 0;
             }
         });
     }

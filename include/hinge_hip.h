@@ -104,6 +104,16 @@ int hinge_get_pileup_facts(hinge_ctx* ctx, uint32_t* max_pile, int* spans_in_ran
  *   or -1 when a coordinate lies outside [0, rlen] or the pile-up has 65 536+ overlaps (the general kernel then takes the read).
  * Without it the library makes them itself, once per hinge_set_pileups, with k_cov_stats.  After hinge_set_pileups[_packed].        */
 int hinge_set_pile_bins(hinge_ctx* ctx, int32_t reso, const int32_t* nbins, int on_device);
+/* ... and one more (the exact-first pass): cov_sum[k], k = 0 .. r_end - r_begin: the SUM of that profile, as int32.  For a read
+ * whose coordinates all lie in [0, rlen] every begin and end event falls inside the profile's bins, so the sum telescopes to
+ *   sum over its overlaps of (aepos / reso - abpos / reso);   0 where nbins[k] == -1.
+ * Valid only after hinge_set_pileups[_packed] and hinge_set_pile_bins at the same reso; dropped by the next hinge_set_pileups.
+ * From the sums, the bins and the read lengths the library works out on the host, here, what filter.cpp:642-678 computes per
+ * part (mean coverage of every read >= 5000 bp, the element of rank n/2, n, the two totals): for on_device != 0 it fetches the
+ * two arrays once for that.  hinge_filter_sweep_batch_async then starts with the exact MIN_COV (see there).  A part with a
+ * read at nbins == -1 keeps the speculative pass: the general kernel defines that read's mean.  HINGE_INGEST_COV=0 in the
+ * environment of hinge_ctx_create: the sums are ignored.                                                                       */
+int hinge_set_pile_cov(hinge_ctx* ctx, int32_t reso, const int32_t* cov_sum, int on_device);
 /* Optional: use a caller-owned DEVICE buffer int32[n_reads][2] as the all-read mask table (so a
  * collective can fill other ranks' rows in place).  NULL returns to the library-owned table.      */
 int hinge_attach_mask_table(hinge_ctx* ctx, int32_t* d_mask_all);
@@ -184,7 +194,13 @@ int hinge_filter_run(hinge_ctx* ctx, const hinge_filter_params* p);
  *   hist_dev + k * row_stride as by hinge_filter_median_hist; the caller all-reduces and calls
  *   hinge_filter_median_from_hist_batch (which verifies) before finish_batch().
  * With delete_telomere != 0 (the telomere test sums max(cov, MIN_COV): no band) or HINGE_ONE_SWEEP=0 the two calls run the
- * two-sweep pass: sweep_batch = stats + median, finish_batch = mask_annotate.                                                */
+ * two-sweep pass: sweep_batch = stats + median, finish_batch = mask_annotate.
+ * EXACT-FIRST: when every part of the batch has the ingest's coverage sums (hinge_set_pile_cov at reso 40, every read with
+ * nbins >= 0), hist_dev == NULL, reso == 40, delete_telomere == 0 and hinge_debug_spec was never called on the contexts,
+ * MIN_COV needs no device sweep: sweep_batch is ONE small launch for all parts (k_exact_begin: clears the pass scalars, applies
+ * a pending MIN_COV, stores the estimate and the totals, MIN_COV = max(MIN_COV, (est_cov ? est_cov : cov_est) / 3) against the
+ * running value, and the means where the table does not hold them yet) followed by K2 with that exact value; finish_batch
+ * launches nothing.  Same results, bit for bit.  hinge_filter_spec_stats then reports [3] = 0, [4] == [5], [0..2] unchanged. */
 int hinge_filter_sweep_batch_async(hinge_ctx** ctxs, int32_t n, const hinge_filter_params* p, uint32_t* hist_dev, int64_t row_stride);
 int hinge_filter_finish_batch_async(hinge_ctx** ctxs, int32_t n, const hinge_filter_params* p);
 /* The same for one part, synchronously: sweep + verification + guard-band reads, the annotation buffer regrown and the pass
@@ -193,7 +209,8 @@ int hinge_filter_finish_batch_async(hinge_ctx** ctxs, int32_t n, const hinge_fil
 int hinge_filter_sweep(hinge_ctx* ctx, const hinge_filter_params* p, hinge_cov_estimate* out);
 /* out[0] one-sweep passes verified so far, [1] of which the exact MIN_COV differed from the prediction, [2] of which it fell
  * outside the band (whole part redone); last pass: [3] reads on the guard-band list (-1: it was a two-sweep pass),
- * [4] predicted MIN_COV, [5] exact MIN_COV.  Synchronises.                                                                   */
+ * [4] predicted MIN_COV, [5] exact MIN_COV.  An exact-first pass verifies nothing: [0..2] stand still, [3] = 0, [4] = [5].
+ * Synchronises.                                                                                                              */
 int hinge_filter_spec_stats(hinge_ctx* ctx, int64_t out[6]);
 /* Tests: band (>= 0; -1 keeps), sample size (> 0; else keeps), bias added to every prediction (forces mispredictions).        */
 int hinge_debug_spec(hinge_ctx* ctx, int band, int sample, int bias);
