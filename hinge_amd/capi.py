@@ -180,6 +180,7 @@ EXTRA_SYMBOLS = [
     ("hinge_debug_long_reads", C.c_int, [_VP, _VP]),
     ("hinge_debug_heavy_items", C.c_int, [_VP, _VP]),
     ("hinge_debug_pileup_order", C.c_int, [_VP, C.c_int32, _VP, _VP]),
+    ("hinge_debug_pileup_order_in", C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP]),
 ]
 
 
@@ -346,6 +347,15 @@ class Context:
         pos = np.zeros(max(len(keys), 1), np.int32)
         self._ck(self.lib.hinge_debug_pileup_order(self.h, len(keys), _ptr(keys), _ptr(pos)))
         return pos[:len(keys)]
+
+    def debug_pileup_order_in(self, cap: int, lean: bool, keys: np.ndarray):
+        """debug_pileup_order through the replay instance of k_hinge_call<cap> (4096, 2048, 1024), lean: the entry that takes its keys
+        from a functor.  Returns (sorted, pos); pos stays all -1 where the entry did not sort (lean, keys spanning 2^20 or more)."""
+        keys = np.ascontiguousarray(keys, dtype=np.int32)
+        pos = np.full(max(len(keys), 1), -1, np.int32)
+        ok = np.full(1, -1, np.int32)
+        self._ck(self.lib.hinge_debug_pileup_order_in(self.h, int(cap), 1 if lean else 0, len(keys), _ptr(keys), _ptr(pos), _ptr(ok)))
+        return bool(ok[0] == 1), pos[:len(keys)]
 
     # ---- filter -------------------------------------------------------------------------------
     def filter_stats(self, p: FilterParams):

@@ -835,7 +835,7 @@ __global__ __launch_bounds__(BLOCK) void k_hinge_call(FilterDev P, HingeBatch B,
                     __syncthreads();
                     block_std_sort_desc(S.ws, n, tid);
                 }
-                if (!sorted) {   // (block-uniform; keys spanning 2^20: the serial exact kernel takes the annotation)
+                if (!sorted) {   // (block-uniform; keys spanning 2^20: the serial exact kernel takes the annotation - launch_hinges_batch launches it for parts with a read of 2^19+ bases)
                     order_valid = false;
                     if (tid == 0) {
                         const unsigned q = atomicAdd(exact_count, 1u);

@@ -692,6 +692,58 @@ int hinge_debug_pileup_order(hinge_ctx* ctx, int32_t n, const int32_t* keys, int
     return HINGE_OK;
 }
 
+// test hook: the same through any instance of the replay's work space - CAP = PO_CAP, PO_CAP_SMALL or PO_CAP_MINI, what k_hinge_call<CAP>
+// sorts in - and either entry: block_std_sort_desc on a key array, or (LEAN) block_std_sort_desc_keys on a functor, the keys staged in
+// pl .. pr.  *sorted_out = whether the entry sorted; pos_out is written only if it did.
+extern "C++" {
+template <int CAP, bool LEAN>
+__global__ __launch_bounds__(256) void k_debug_pileup_order_in(const int* __restrict__ keys, int n, int* __restrict__ pos_out, int* __restrict__ sorted_out) {
+    __shared__ WaveSortLdsT<CAP, LEAN> po;
+    const int tid = threadIdx.x;
+    bool sorted = true;
+    if constexpr (LEAN) {
+        sorted = block_std_sort_desc_keys(po, n, tid, [&](int p) { return keys[p]; });
+    } else {
+        for (int k = tid; k < n; k += 256) po.key[k] = keys[k];
+        __syncthreads();
+        block_std_sort_desc(po, n, tid);
+    }
+    if (tid == 0) *sorted_out = sorted ? 1 : 0;
+    if (sorted) for (int k = tid; k < n; k += 256) pos_out[k] = po.pl[k];
+}
+}   // extern "C++"
+
+int hinge_debug_pileup_order_in(hinge_ctx* ctx, int32_t cap, int32_t lean, int32_t n, const int32_t* keys, int32_t* pos_out, int32_t* sorted_out) {
+    if (!ctx || (cap != PO_CAP && cap != PO_CAP_SMALL && cap != PO_CAP_MINI) || (lean != 0 && lean != 1) || n < 0 || n > cap || !keys || !pos_out || !sorted_out)
+        return fail(ctx, HINGE_E_ARG, "hinge_debug_pileup_order_in: bad arguments");
+    CK(hipSetDevice(ctx->device));
+    int *dk = nullptr, *dp = nullptr;    // dp[n] = the sorted flag; dp[0..n) starts as the caller's pos_out, so what the kernel leaves alone comes back unchanged
+    CK(hipMalloc(&dk, sizeof(int) * (size_t)std::max(n, 1)));
+    CK(hipMalloc(&dp, sizeof(int) * (size_t)(n + 1)));
+    int rc = HINGE_OK;
+    const int minus = -1;
+    hipError_t e = hipMemcpy(dk, keys, sizeof(int) * (size_t)n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dp, pos_out, sizeof(int) * (size_t)n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dp + n, &minus, sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const dim3 g(1), b(256);
+        if (cap == PO_CAP && !lean) hipLaunchKernelGGL((k_debug_pileup_order_in<PO_CAP, false>), g, b, 0, ctx->stream, (const int*)dk, n, dp, dp + n);
+        else if (cap == PO_CAP) hipLaunchKernelGGL((k_debug_pileup_order_in<PO_CAP, true>), g, b, 0, ctx->stream, (const int*)dk, n, dp, dp + n);
+        else if (cap == PO_CAP_SMALL && !lean) hipLaunchKernelGGL((k_debug_pileup_order_in<PO_CAP_SMALL, false>), g, b, 0, ctx->stream, (const int*)dk, n, dp, dp + n);
+        else if (cap == PO_CAP_SMALL) hipLaunchKernelGGL((k_debug_pileup_order_in<PO_CAP_SMALL, true>), g, b, 0, ctx->stream, (const int*)dk, n, dp, dp + n);
+        else if (!lean) hipLaunchKernelGGL((k_debug_pileup_order_in<PO_CAP_MINI, false>), g, b, 0, ctx->stream, (const int*)dk, n, dp, dp + n);
+        else hipLaunchKernelGGL((k_debug_pileup_order_in<PO_CAP_MINI, true>), g, b, 0, ctx->stream, (const int*)dk, n, dp, dp + n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = hipMemcpy(pos_out, dp, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(sorted_out, dp + n, sizeof(int), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(ctx, HINGE_E_DEVICE, hipGetErrorString(e));
+    (void)hipFree(dk);
+    (void)hipFree(dp);
+    return rc;
+}
+
 // hidden knob for tests: run the general K2 kernel even where k_mask_annotate_q20 applies
 // (also: environment HINGE_DEBUG_GENERAL_MASK=1 when the context is created, for the executables)
 int hinge_debug_force_general_mask(hinge_ctx* ctx, int on) {
@@ -1592,6 +1644,7 @@ static int launch_hinges_batch(hinge_ctx** ctxs, int n, const hinge_filter_param
     // it passes on - the tie order decides, or more than LIGHT_CAP supporters - goes through the instances that can replay the sort
     bool light = ctx->hinge_light != 0;
     for (int k = 0; k < n; k++) light = light && ctxs[k]->force_exact == 0;
+    bool lean_ran = false;       // the LEAN instance is in this pass: it can hand annotations to the exact queue
     { ProfScope _ps(ctx, KID_HINGE_CALL);
     if (light) {
         if (ctx->light_occ == 0) {
@@ -1618,15 +1671,21 @@ static int launch_hinges_batch(hinge_ctx** ctxs, int n, const hinge_filter_param
         hipLaunchKernelGGL(k_hinge_call<PO_CAP>, dim3(std::max(n, (ctx->n_cu / n) * n)), dim3(BLOCK), 0, ctx->stream, to_dev(p), B, 1, 2, n_min, INT_MAX, 0);
     } else {
         // behind the light kernel: the LEAN instance (52 KiB of LDS: three workgroups per CU; HINGE_CALL_LEAN=0: the full one, two per CU)
-        if (light && ctx->hinge_lean) hipLaunchKernelGGL((k_hinge_call<PO_CAP_SMALL, true>), dim3(std::max(n, (3 * ctx->n_cu / n) * n)), dim3(BLOCK), 0, ctx->stream, to_dev(p), B, 0, 1, n_min, INT_MAX, 0);
+        lean_ran = light && ctx->hinge_lean;
+        if (lean_ran) hipLaunchKernelGGL((k_hinge_call<PO_CAP_SMALL, true>), dim3(std::max(n, (3 * ctx->n_cu / n) * n)), dim3(BLOCK), 0, ctx->stream, to_dev(p), B, 0, 1, n_min, INT_MAX, 0);
         else hipLaunchKernelGGL(k_hinge_call<PO_CAP_SMALL>, dim3(std::max(n, (2 * ctx->n_cu / n) * n)), dim3(BLOCK), 0, ctx->stream, to_dev(p), B, 0, light ? 1 : 0, n_min, INT_MAX, 0);
         if (any_big) hipLaunchKernelGGL(k_hinge_call<PO_CAP>, dim3(std::max(n, (ctx->n_cu / n) * n)), dim3(BLOCK), 0, ctx->stream, to_dev(p), B, 1, 0, 0, INT_MAX, 0);
     } }
     CK(hipGetLastError());
-    // the serial exact path takes pile-ups or supporter lists beyond PO_CAP (and everything under force_exact == 1): per part
+    // the serial exact path takes pile-ups or supporter lists beyond PO_CAP (and everything under force_exact == 1): per part.
+    // It also takes what the LEAN instance hands over because its keys span 2^(32 - PK_SHIFT) or more (block_std_sort_desc_keys
+    // returned false).  A pile-up key is a sum of two span lengths, a supporter key a position on the read: with the spans inside
+    // their reads no list spans more than twice the longest read, so only a part with a read of 2^19 bases or more (or with spans
+    // outside their reads) can queue such an annotation, and only such a part pays the launch.
     for (int k = 0; k < n; k++) {
         hinge_ctx* c = ctxs[k];
-        if (c->max_pile <= (unsigned)PO_CAP && c->force_exact != 1) continue;
+        const bool lean_can_refuse = lean_ran && (!c->spans_in_range || 2ll * (long long)c->max_rlen >= (1ll << (32 - PK_SHIFT)));
+        if (c->max_pile <= (unsigned)PO_CAP && c->force_exact != 1 && !lean_can_refuse) continue;
         ProfScope _ps2(ctx, KID_HINGE_EXACT);
         hipLaunchKernelGGL(k_hinge_exact, dim3(64), dim3(64), 0, ctx->stream, to_dev(p), (const int64_t*)c->row_ptr.p,
                            (const int2*)c->a_span.p, (const int2*)c->b_span.p, (const unsigned*)c->b_flag.p, (const int2*)c->mask,

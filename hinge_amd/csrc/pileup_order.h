@@ -526,8 +526,9 @@ __device__ inline void block_std_sort_desc(WS& o, int n, int tid) {
 
 // The same for a list whose keys come from a functor (the LEAN work space has no key array): the keys are staged once in the stopper
 // scratch (pl .. pr: CAP ints, free until the walk starts), their range is reduced, the packed words are built from the stage.
-// Returns false - nothing sorted - when the keys span 2^(32 - PK_SHIFT) or more (the caller takes another route: never seen on
-// length sums or other ends, both below 2^18).  Call from ALL threads of a 256-thread workgroup.
+// Returns false - nothing sorted, pl .. pr hold the staged keys - when the keys span 2^(32 - PK_SHIFT) or more: the caller takes
+// another route (k_hinge_call files the annotation for k_hinge_exact).  Length sums and other ends get there on a read of 2^19
+// bases or more; launch_hinges_batch launches the exact kernel for such parts.  Call from ALL threads of a 256-thread workgroup.
 template <typename WS, typename KeyOf>
 __device__ inline bool block_std_sort_desc_keys(WS& o, int n, int tid, KeyOf key_of) {
     static_assert(sizeof(o.pl) == sizeof(o.pr), "pl and pr: one stretch of CAP ints");

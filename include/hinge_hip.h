@@ -580,6 +580,11 @@ int hinge_debug_long_reads(hinge_ctx* ctx, int64_t* out);
 int hinge_debug_heavy_items(hinge_ctx* ctx, int64_t* out);
 /* pos_out[k] = position of element k after std::sort(compare_overlap) of n keys, through the wavefront-parallel replay. */
 int hinge_debug_pileup_order(hinge_ctx* ctx, int32_t n, const int32_t* keys, int32_t* pos_out);
+/* The same through a chosen instance of the replay: cap = 4096, 2048 or 1024 (the work space of k_hinge_call<cap>); lean 0 = the entry
+ * above on a key array, 1 = the entry of the LEAN work space, which has no key array (the keys come from a functor and are staged in
+ * the stopper scratch).  *sorted_out = 1 and pos_out as above, or 0 - the lean entry refuses keys that span 2^20 or more - with
+ * pos_out left as it was.  HINGE_E_ARG: n > cap, another cap. */
+int hinge_debug_pileup_order_in(hinge_ctx* ctx, int32_t cap, int32_t lean, int32_t n, const int32_t* keys, int32_t* pos_out, int32_t* sorted_out);
 
 #ifdef __cplusplus
 }

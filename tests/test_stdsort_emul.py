@@ -1,53 +1,16 @@
 """hinge_amd/csrc/stdsort_emul.h (the host/device replay of libstdc++ std::sort the HIP kernels use)
 compiled for the host and compared with the real std::sort (through the oracle library)."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ip = ctypes.POINTER(ctypes.c_int)
-P = lambda a: a.ctypes.data_as(ip)  # noqa: E731
+from sort_killer_common import P
 
-HARNESS = r'''
-#include <algorithm>
-#include <vector>
-#include "stdsort_emul.h"
-extern "C" void emul_sort_perm(int n, const int* key, int desc, int* perm) {
-    for (int i = 0; i < n; i++) perm[i] = i;
-    hinge_sort::std_sort(perm, n, key, desc);
-}
-// McIlroy's "antiquicksort" adversary run against std::sort: produces keys that drive the
-// median-of-3 introsort into its depth limit (the heapsort fallback).
-static std::vector<int> val; static int nsolid, candidate, gas;
-static bool adv_cmp(int x, int y) {
-    if (val[x] == gas && val[y] == gas) { if (x == candidate) val[x] = nsolid++; else val[y] = nsolid++; }
-    if (val[x] == gas) candidate = x; else if (val[y] == gas) candidate = y;
-    return val[x] < val[y];
-}
-extern "C" void killer_keys(int n, int* out) {
-    val.assign(n, 0); gas = n - 1; nsolid = 0; candidate = 0;
-    std::vector<int> idx(n);
-    for (int i = 0; i < n; i++) { idx[i] = i; val[i] = gas; }
-    std::sort(idx.begin(), idx.end(), adv_cmp);
-    for (int i = 0; i < n; i++) out[i] = val[i];
-}
-'''
+import sort_killer_common as skc
 
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    d = tmp_path_factory.mktemp("emul")
-    src = d / "h.cpp"
-    src.write_text(HARNESS)
-    so = d / "h.so"
-    subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-I", os.path.join(ROOT, "hinge_amd", "csrc"), "-o", str(so), str(src)])
-    lib = ctypes.CDLL(str(so))
-    lib.emul_sort_perm.argtypes = [ctypes.c_int, ip, ctypes.c_int, ip]
-    lib.killer_keys.argtypes = [ctypes.c_int, ip]
-    return lib
+    return skc.harness(tmp_path_factory)
 
 
 def _check(emul, oracle_lib, key):
@@ -77,3 +40,17 @@ def test_replay_matches_std_sort_in_heapsort_fallback(emul, oracle_lib):
         emul.killer_keys(n, P(k))
         _check(emul, oracle_lib, k)            # ascending comparator = the adversary's own
         _check(emul, oracle_lib, -k)
+
+
+@pytest.mark.parametrize("n,q", skc.CASES)
+def test_replay_matches_std_sort_in_heapsort_fallback_with_ties(emul, oracle_lib, n, q):
+    """Killer keys with ties (key = -(val // q), descending): the case reaches the depth limit where sort_killer_common says it
+    does, for q >= 2 the heap part's tie order shows in the result, and hinge_sort::std_sort leaves the order of std::sort."""
+    skc.assert_case_reaches_the_fallback(emul, n, q)
+    key = skc.killer_key(emul, n, q)
+    got = np.zeros(n, np.int32)
+    emul.emul_sort_perm(n, P(key), 1, P(got))
+    assert np.array_equal(got, skc.oracle_perm(oracle_lib, key)), (n, q)
+    wide = key * (1 << 19)                      # what the GPU test feeds the wide form: the same comparisons
+    assert wide.dtype == np.int32 and int(wide.max()) - int(wide.min()) >= 1 << 20
+    assert np.array_equal(skc.oracle_perm(oracle_lib, wide), got), (n, q, "wide")
