@@ -12,7 +12,7 @@ LIB  = hinge_amd/lib/libhinge_hip.so
 BIN  = hinge_amd/bin
 HOST = hinge_amd/host
 HOSTDEPS = $(wildcard $(HOST)/*.h) include/hinge_hip.h $(LIB)
-PROGS = $(BIN)/Reads_filter $(BIN)/get_maximal_reads $(BIN)/hinging $(BIN)/consensus $(BIN)/draft_assembly $(BIN)/paf2las $(BIN)/seed $(BIN)/hinge_pipeline $(BIN)/hinge
+PROGS = $(BIN)/Reads_filter $(BIN)/get_maximal_reads $(BIN)/hinging $(BIN)/consensus $(BIN)/draft_assembly $(BIN)/paf2las $(BIN)/seed $(BIN)/overlap $(BIN)/hinge_pipeline $(BIN)/hinge
 
 SYNTHIO = hinge_amd/lib/libhinge_synthio.so
 
@@ -47,6 +47,10 @@ $(BIN)/paf2las: $(HOST)/paf2las_main.cpp $(HOSTDEPS)
 	$(HIPCC) -O2 -std=c++17 -w -pthread -o $@ $< -Lhinge_amd/lib -lhinge_hip -lz -Wl,-rpath,'$$ORIGIN/../lib'
 
 $(BIN)/seed: $(HOST)/seed_main.cpp $(HOSTDEPS)
+	mkdir -p $(BIN)
+	$(HIPCC) -O2 -std=c++17 -w -pthread -o $@ $< -Lhinge_amd/lib -lhinge_hip -lz -Wl,-rpath,'$$ORIGIN/../lib'
+
+$(BIN)/overlap: $(HOST)/overlap_main.cpp $(HOSTDEPS)
 	mkdir -p $(BIN)
 	$(HIPCC) -O2 -std=c++17 -w -pthread -o $@ $< -Lhinge_amd/lib -lhinge_hip -lz -Wl,-rpath,'$$ORIGIN/../lib'
 

@@ -122,6 +122,9 @@ SYMBOLS = [
     ("hinge_seed_run", C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_int64)]),
     ("hinge_seed_db_reads", C.c_int, [_VP, C.POINTER(C.c_int64)]),
     ("hinge_seed_last_stats", C.c_int, [_VP, _VP]),
+    ("hinge_overlap_run", C.c_int, [_VP, _VP, _VP, _VP, C.POINTER(C.c_int64)]),
+    ("hinge_overlap_fetch", C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, _VP]),
+    ("hinge_overlap_last_stats", C.c_int, [_VP, _VP]),
     ("hinge_profile_report", C.c_int, [_VP, _VP, _VP]),
     ("hinge_timer_start", C.c_int, [_VP]),
     ("hinge_timer_stop_ms", C.c_int, [_VP, C.POINTER(C.c_float)]),
@@ -627,6 +630,37 @@ class Context:
         self._ck(self.lib.hinge_seed_last_stats(self.h, _ptr(st)))
         return dict(zip(("jobs", "batches", "entries", "dropped_codes", "overflow", "unplaced", "index_us"), [int(v) for v in st[:7]]))
 
+    def overlap_run(self, k: int = 0, step: int = 0, window: int = 0, max_occ: int = 0, list_: int = 0, max_partners: int = 0, min_hits: int = 0, block_bases: int = 0):
+        """hinge_overlap_run (`hinge overlap`): read-vs-read overlap candidates of the reads of Consensus(ctx, read_db, read_db) by
+        k-mer votes.  0 = the default (HINGE_OVERLAP_*, else 15, 2, 256, 64, 4096, 64, 6, 16 Mi).  Returns (candidates int64 [m, 7] =
+        rows of (aread, bread, comp, abpos, aepos, bbpos, bepos) as trace_local takes them, sorted by (aread, bread, comp), count
+        int32 [m], diag int32 [m] = bbpos - abpos, rep int32 [m, 2] = the representative's (d, p), status int32 [n, 2] = per strand 1 NONE,
+        else the bits 2 OVERFLOW and 4 TRUNCATED, hits int32 [n, 2] = hits kept) and leaves the call's figures in overlap_stats()."""
+        nr = C.c_int64(0)
+        self._ck(self.lib.hinge_seed_db_reads(self.h, C.byref(nr)))
+        n = int(nr.value)
+        status = np.zeros((max(n, 1), 2), dtype=np.int32)
+        params = np.zeros(1, dtype=OVERLAP_PARAMS_DTYPE)
+        params[0] = (k, step, window, max_occ, list_, max_partners, min_hits, 0, block_bases)
+        m = C.c_int64(0)
+        hits = np.zeros((max(n, 1), 2), dtype=np.int32)
+        self._ck(self.lib.hinge_overlap_run(self.h, _ptr(params), _ptr(status), _ptr(hits), C.byref(m)))
+        m = m.value
+        out = np.zeros(max(m, 1), dtype=CNS_ALN_DTYPE)
+        count = np.zeros(max(m, 1), dtype=np.int32)
+        diag = np.zeros(max(m, 1), dtype=np.int32)
+        rep = np.zeros((max(m, 1), 2), dtype=np.int32)
+        self._ck(self.lib.hinge_overlap_fetch(self.h, m, _ptr(out), _ptr(count), _ptr(diag), _ptr(rep)))
+        pl = np.stack([out[name][:m].astype(np.int64) for name in ("aread", "bread", "comp", "abpos", "aepos", "bbpos", "bepos")], axis=1) if m else np.zeros((0, 7), np.int64)
+        return pl, count[:m], diag[:m], rep[:m], status[:n], hits[:n]
+
+    def overlap_stats(self) -> dict:
+        """Of the last overlap_run: jobs (read, strand, block), batches, blocks, index entries, codes dropped by max_occ, OVERFLOW
+        jobs, TRUNCATED jobs, and the microseconds the indexes took (host build, upload)."""
+        st = np.zeros(8, np.int64)
+        self._ck(self.lib.hinge_overlap_last_stats(self.h, _ptr(st)))
+        return dict(zip(("jobs", "batches", "blocks", "entries", "dropped_codes", "overflow", "truncated", "index_us"), [int(v) for v in st[:8]]))
+
     def profile_enable(self, max_launches: int):
         self._ck(self.lib.hinge_profile_enable(self.h, int(max_launches)))
 
@@ -657,6 +691,7 @@ class Context:
 
 CNS_ALN_DTYPE = np.dtype([("aread", "<i4"), ("bread", "<i4"), ("comp", "<i4"), ("abpos", "<i4"), ("aepos", "<i4"), ("bbpos", "<i4"), ("bepos", "<i4"),
                           ("tlen", "<i4"), ("trace_off", "<i8")])   # hinge_cns_alignment
+OVERLAP_PARAMS_DTYPE = np.dtype([(n, "<i4") for n in ("k", "step", "window", "max_occ", "list", "max_partners", "min_hits", "pad")] + [("block_bases", "<i8")])   # hinge_overlap_params
 
 
 class CnsStats(C.Structure):

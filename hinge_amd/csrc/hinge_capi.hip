@@ -20,6 +20,7 @@
 #include "trace_kernels.h"
 #include "seed_kernels.h"
 #include "seed_index.h"
+#include "overlap_kernels.h"
 
 using namespace hinge;
 
@@ -159,6 +160,7 @@ struct hinge_ctx {
     struct DraftState* draft = nullptr; // `hinge draft` (draft_capi.inc)
     struct TraceState* trace_st = nullptr;   // `hinge paf2las` (trace_capi.inc)
     struct SeedState* seed_st = nullptr;     // `hinge seed` (seed_capi.inc)
+    struct OverlapState* ovl_st = nullptr;   // `hinge overlap` (overlap_capi.inc)
     void* comm = nullptr;               // ncclComm_t of this context among the contexts of its process (comm_capi.inc)
     int comm_rank = -1, comm_size = 0;
     DevBuf comm_stage;                  // all-gathered mask rows [comm_size + 1][S][2]
@@ -168,10 +170,10 @@ struct hinge_ctx {
 };
 
 enum KernelId { KID_STATS = 0, KID_MEDIAN, KID_MASK_ANNOTATE, KID_MASK_FALLBACK, KID_HINGE_COUNT, KID_HINGE_CALL, KID_HINGE_EXACT, KID_COVERAGE_BINS, KID_TRIM_CLASSIFY,
-                KID_PILEUP_FACTS, KID_MATCHING_POSITION, KID_SELECT_EDGES, KID_SPEC_PREDICT, KID_MASK_FINAL, KID_CNS_REALIGN, KID_CNS_COLUMNS, KID_CNS_VOTE, KID_CNS_CALL, KID_DRAFT_ALIGN, KID_DRAFT_CNS, KID_DRAFT_ALIGN_LONG, KID_DRAFT_CNS_DEEP, KID_MASK_LONG, KID_TRACE_FILL, KID_TRACE_WALK, KID_TRACE_CLIP, KID_TRACE_FILL_LOCAL, KID_TRACE_WALK_LOCAL, KID_SEED_VOTE, KID_EXACT_BEGIN, KID_COUNT };
+                KID_PILEUP_FACTS, KID_MATCHING_POSITION, KID_SELECT_EDGES, KID_SPEC_PREDICT, KID_MASK_FINAL, KID_CNS_REALIGN, KID_CNS_COLUMNS, KID_CNS_VOTE, KID_CNS_CALL, KID_DRAFT_ALIGN, KID_DRAFT_CNS, KID_DRAFT_ALIGN_LONG, KID_DRAFT_CNS_DEEP, KID_MASK_LONG, KID_TRACE_FILL, KID_TRACE_WALK, KID_TRACE_CLIP, KID_TRACE_FILL_LOCAL, KID_TRACE_WALK_LOCAL, KID_SEED_VOTE, KID_EXACT_BEGIN, KID_OVERLAP_VOTE, KID_COUNT };
 static const char* const KERNEL_NAMES[KID_COUNT] = {"k_cov_stats", "k_median_hist", "k_mask_annotate", "k_mask_annotate_fallback", "k_hinge_count", "k_hinge_call", "k_hinge_exact",
                                                      "k_coverage_bins", "k_trim_classify", "k_pileup_facts", "k_matching_position", "k_select_edges", "k_spec_predict",
-                                                     "k_mask_annotate_final", "k_cns_realign", "k_cns_columns", "k_cns_vote", "k_cns_call", "k_draft_align", "k_draft_cns", "k_draft_align_long", "k_draft_cns_deep", "k_mask_annotate_long", "k_trace_fill", "k_trace_walk", "k_trace_clip", "k_trace_fill_local", "k_trace_walk_local", "k_seed_vote", "k_exact_begin"};
+                                                     "k_mask_annotate_final", "k_cns_realign", "k_cns_columns", "k_cns_vote", "k_cns_call", "k_draft_align", "k_draft_cns", "k_draft_align_long", "k_draft_cns_deep", "k_mask_annotate_long", "k_trace_fill", "k_trace_walk", "k_trace_clip", "k_trace_fill_local", "k_trace_walk_local", "k_seed_vote", "k_exact_begin", "k_overlap_vote"};
 
 struct ProfScope {
     hinge_ctx* c;
@@ -346,6 +348,7 @@ static void cns_release(hinge_ctx* ctx);
 static void draft_release(hinge_ctx* ctx);
 static void trace_release(hinge_ctx* ctx);
 static void seed_release(hinge_ctx* ctx);
+static void overlap_release(hinge_ctx* ctx);
 static void comm_release(hinge_ctx* ctx);
 void hinge_ctx_destroy(hinge_ctx* ctx) {
     if (!ctx) return;
@@ -354,6 +357,7 @@ void hinge_ctx_destroy(hinge_ctx* ctx) {
     draft_release(ctx);
     trace_release(ctx);
     seed_release(ctx);
+    overlap_release(ctx);
     comm_release(ctx);
     DevBuf* all[] = {&ctx->rlen, &ctx->qv_mask, &ctx->row_ptr, &ctx->a_span, &ctx->b_span, &ctx->b_flag, &ctx->mask_own, &ctx->mean_own,
                      &ctx->cmask, &ctx->rflags, &ctx->nbins0, &ctx->anno_buf, &ctx->anno_off, &ctx->anno_cnt, &ctx->hinge_flag,
@@ -2256,6 +2260,7 @@ int hinge_timer_stop_ms(hinge_ctx* ctx, float* ms) {
 #include "draft_capi.inc"
 #include "trace_capi.inc"
 #include "seed_capi.inc"
+#include "overlap_capi.inc"
 #include "comm_capi.inc"
 
 #ifdef HINGE_K2_TRACE

@@ -1,0 +1,192 @@
+// C ABI of `hinge overlap` (include/hinge_hip.h, "hinge overlap").  Included by hinge_capi.hip.
+// Host work here: the parameters' defaults and ranges, the limits of the key packing, the target blocks and their k-mer indexes
+// (seed_index.h; built from the host copy of DB 0's bases that hinge_consensus_set_db keeps, one block resident at a time), the
+// jobs (two per read) in batches under the scratch budget against every block, a candidate's projection in the record's frame
+// (overlap_project) and the order of the result.  The kernel: overlap_kernels.h.
+
+struct OverlapCand { hinge_cns_alignment r; int32_t cnt, diag, d, p; };
+struct OverlapState {
+    DevBuf jobs, out, codes, gpos, off;
+    std::vector<OverlapCand> cand;                 // of the last hinge_overlap_run, sorted by (a, b, comp)
+    int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // hinge_overlap_last_stats
+};
+
+static void overlap_release(hinge_ctx* ctx) {
+    OverlapState* t = ctx->ovl_st;
+    if (!t) return;
+    DevBuf* all[] = {&t->jobs, &t->out, &t->codes, &t->gpos, &t->off};
+    for (DevBuf* b : all) release(*b);
+    delete t;
+    ctx->ovl_st = nullptr;
+}
+
+// One batch: jobs[0..nj) through k_overlap_vote against the resident block; h_out = ovl_out_ints(max_partners) ints per job.
+static int overlap_batch(hinge_ctx* ctx, const OvlJob* jobs, size_t nj, const OvlParams& P, std::vector<int>& h_out) {
+    OverlapState* t = ctx->ovl_st;
+    CnsState* s = ctx->cns;
+    const size_t out_ints = nj * (size_t)ovl_out_ints(P.max_partners);
+    int rc;
+    if ((rc = ensure(ctx, t->jobs, sizeof(OvlJob) * nj))) return rc;
+    if ((rc = ensure(ctx, t->out, sizeof(int) * out_ints))) return rc;
+    CK(hipMemcpyAsync(t->jobs.p, jobs, sizeof(OvlJob) * nj, hipMemcpyHostToDevice, ctx->stream));
+    CK(hipMemsetAsync(t->out.p, 0xff, sizeof(int) * out_ints, ctx->stream));   // poison: a slot the kernel did not write is seen as such
+    CnsSeqs SB{(const unsigned char*)s->bps[0].p, (const long long*)s->boff[0].p, (const int*)s->rlen[0].p};
+    {
+        ProfScope _ps(ctx, KID_OVERLAP_VOTE);
+        hipLaunchKernelGGL(k_overlap_vote, dim3((unsigned)nj), dim3(64), ovl_lds_bytes(P.list), ctx->stream, SB, (const OvlJob*)t->jobs.p, (int)nj, P, (const unsigned*)t->codes.p,
+                           (const int*)t->gpos.p, (const long long*)t->off.p, (int*)t->out.p);
+    }
+    CK(hipGetLastError());
+    h_out.resize(out_ints);
+    CK(hipMemcpyAsync(h_out.data(), t->out.p, sizeof(int) * out_ints, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    return HINGE_OK;
+}
+
+extern "C" {
+
+int hinge_overlap_run(hinge_ctx* ctx, const hinge_overlap_params* params, int32_t* status, int32_t* hits, int64_t* n_out) {
+    if (!ctx || !ctx->cns || !n_out || (ctx->cns->n_seq[0] > 0 && !status))
+        return fail(ctx, HINGE_E_ARG, "hinge_overlap_run: bad arguments (call hinge_consensus_set_db with the read DB for both DBs first)");
+    hinge_overlap_params q = params ? *params : hinge_overlap_params{0, 0, 0, 0, 0, 0, 0, 0};
+    if (q.k == 0) q.k = (int32_t)seed_env("HINGE_OVERLAP_K", 15);
+    if (q.step == 0) q.step = (int32_t)seed_env("HINGE_OVERLAP_STEP", 2);
+    if (q.window == 0) q.window = (int32_t)seed_env("HINGE_OVERLAP_WINDOW", 256);
+    if (q.max_occ == 0) q.max_occ = (int32_t)seed_env("HINGE_OVERLAP_MAX_OCC", HINGE_OVERLAP_MAX_OCC);
+    if (q.list == 0) q.list = (int32_t)seed_env("HINGE_OVERLAP_LIST", 4096);
+    if (q.max_partners == 0) q.max_partners = (int32_t)seed_env("HINGE_OVERLAP_MAX_PARTNERS", 64);
+    if (q.min_hits == 0) q.min_hits = (int32_t)seed_env("HINGE_OVERLAP_MIN_HITS", HINGE_OVERLAP_MIN_HITS);
+    if (q.block_bases == 0) q.block_bases = (int64_t)seed_env("HINGE_OVERLAP_BLOCK_BASES", 16ll << 20);
+    auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
+    if (q.k < SEED_K_MIN || q.k > SEED_K_MAX || q.step < 1 || q.step > 65536 || !pow2(q.window) || q.window < SEED_WINDOW_MIN || q.window > SEED_WINDOW_MAX || q.max_occ < 1 ||
+        q.max_occ > SEED_OCC_MAX || !pow2(q.list) || q.list < OVL_LIST_MIN || q.list > OVL_LIST_MAX || q.max_partners < 1 || q.max_partners > OVL_PARTNERS_MAX || q.min_hits < 1 ||
+        q.block_bases < 1 || q.block_bases >= (1ll << 31))
+        return fail(ctx, HINGE_E_ARG, "hinge_overlap_run: k 8..16, step 1..65536, window a power of two 16..65536, max_occ 1..256, list a power of two 64..8192, max_partners 1..4096, min_hits >= 1, block_bases 1..2^31-1 (0 = the default)");
+    CnsState* s = ctx->cns;
+    const int n = s->n_seq[0];
+    if (s->n_seq[1] != n || s->h_rlen[1] != s->h_rlen[0]) return fail(ctx, HINGE_E_ARG, "hinge_overlap_run: both DBs of hinge_consensus_set_db must be the read DB");
+    // ---- the limits of the key packing, before any launch; the blocks: consecutive reads of at most block_bases bases (a longer read: alone) -------------------
+    std::vector<int> bfirst;                        // [n_blocks + 1]
+    {
+        long long bases = 0;
+        int reads = 0;
+        for (int r = 0; r < n; r++) {
+            const int len = s->h_rlen[0][(size_t)r];
+            if (len > OVL_READ_MAX) return fail(ctx, HINGE_E_CAPACITY, "hinge_overlap_run: a read of 2^20 or more bases (the hit key holds a position in 20 bits)");
+            if (r == 0 || bases + len > q.block_bases || reads == OVL_BLOCK_READS_MAX) { bfirst.push_back(r); bases = 0; reads = 0; }
+            bases += len; reads++;
+            if (bases >= (1ll << 31)) return fail(ctx, HINGE_E_CAPACITY, "hinge_overlap_run: a block of 2^31 or more bases");
+        }
+        bfirst.push_back(n);
+    }
+    const int n_blocks = (int)bfirst.size() - 1;
+    CK(hipSetDevice(ctx->device));
+    if (!ctx->ovl_st) ctx->ovl_st = new OverlapState();
+    OverlapState* t = ctx->ovl_st;
+    for (int64_t& v : t->stats) v = 0;
+    t->cand.clear();
+    *n_out = 0;
+    for (int r = 0; r < 2 * n; r++) { status[r] = OVL_ST_NONE; if (hits) hits[r] = 0; }
+    if (n == 0) return HINGE_OK;
+    const size_t lds = ovl_lds_bytes(q.list);
+    if (lds > 48 * 1024) CK(hipFuncSetAttribute((const void*)k_overlap_vote, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    OvlParams P;
+    P.k = q.k; P.window = q.window; P.max_occ = q.max_occ; P.list = q.list; P.max_partners = q.max_partners; P.min_hits = q.min_hits;
+    // ---- the jobs: two per read, the same for every block ------------------------------------------------------------------------------------
+    std::vector<OvlJob> jobs((size_t)(2 * n));
+    for (int a = 0; a < n; a++) {
+        const int alen = s->h_rlen[0][(size_t)a];
+        for (int comp = 0; comp < 2; comp++) jobs[(size_t)(2 * a + comp)] = OvlJob{a, comp, alen, alen >= q.k ? seed_stride(alen, q.k, q.step, q.list) : q.step};
+    }
+    long long budget = std::max(1ll, seed_env("HINGE_OVERLAP_SCRATCH_MB", 256)) << 20;
+    budget = std::max(1ll, seed_env("HINGE_OVERLAP_SCRATCH_BYTES", budget));
+    const int W = ovl_out_ints(q.max_partners);
+    const long long per_job = (long long)sizeof(OvlJob) + (long long)sizeof(int) * W;
+    const int64_t per_batch = std::min<long long>(std::max<long long>(budget / per_job, 1), 1 << 20);
+    std::vector<int> h_out;
+    int rc;
+    for (int blk = 0; blk < n_blocks; blk++) {
+        // ---- the block's index, the entries up ----------------------------------------------------------------------------------------------------
+        const auto t0 = std::chrono::steady_clock::now();
+        const int first = bfirst[(size_t)blk], nr = bfirst[(size_t)blk + 1] - first;
+        SeedIndex ix;
+        seed_build_index(s->h_bps0.data(), s->h_boff0.data() + first, s->h_rlen[0].data() + first, nr, q.k, q.max_occ, ix);
+        const size_t ne = ix.codes.size();
+        if ((rc = ensure(ctx, t->codes, sizeof(uint32_t) * std::max<size_t>(ne, 1)))) return rc;
+        if ((rc = ensure(ctx, t->gpos, sizeof(int32_t) * std::max<size_t>(ne, 1)))) return rc;
+        if ((rc = ensure(ctx, t->off, sizeof(long long) * ((size_t)nr + 1)))) return rc;
+        if (ne) {
+            CK(hipMemcpyAsync(t->codes.p, ix.codes.data(), sizeof(uint32_t) * ne, hipMemcpyHostToDevice, ctx->stream));
+            CK(hipMemcpyAsync(t->gpos.p, ix.gpos.data(), sizeof(int32_t) * ne, hipMemcpyHostToDevice, ctx->stream));
+        }
+        CK(hipMemcpyAsync(t->off.p, ix.off.data(), sizeof(long long) * ((size_t)nr + 1), hipMemcpyHostToDevice, ctx->stream));
+        CK(hipStreamSynchronize(ctx->stream));
+        t->stats[2]++;
+        t->stats[3] += (int64_t)ne;
+        t->stats[4] += ix.dropped_codes;
+        t->stats[7] += (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+        P.n_entries = (int)ne;
+        P.search_top = 0;
+        for (long long v = 1; v <= (long long)ne; v <<= 1) P.search_top = (int)v;      // the searches' trip counts: fixed here, from the block
+        P.first = first; P.n_reads = nr;
+        P.read_top = 0;
+        for (long long v = 1; v <= (long long)nr; v <<= 1) P.read_top = (int)v;
+        // ---- every job against it, in batches under the scratch budget -------------------------------------------------------------------------------
+        for (int64_t j0 = 0; j0 < 2 * (int64_t)n; j0 += per_batch) {
+            const int64_t j1 = std::min<int64_t>(2 * (int64_t)n, j0 + per_batch);
+            if ((rc = overlap_batch(ctx, jobs.data() + j0, (size_t)(j1 - j0), P, h_out))) return rc;
+            t->stats[0] += j1 - j0;
+            t->stats[1]++;
+            for (int64_t j = j0; j < j1; j++) {
+                const int* o = h_out.data() + (size_t)(j - j0) * (size_t)W;
+                const OvlJob& J = jobs[(size_t)j];
+                const bool st_ok = o[0] == OVL_ST_OK || o[0] == OVL_ST_NONE || o[0] == OVL_ST_OVERFLOW || o[0] == OVL_ST_TRUNCATED || o[0] == (OVL_ST_OVERFLOW | OVL_ST_TRUNCATED);
+                if (!st_ok || o[1] < 0 || o[1] > q.max_partners || o[2] < 0 || o[2] > q.list || (o[1] > 0 && (o[2] < 1 || o[0] == OVL_ST_NONE)) || o[3] != 0)
+                    return fail(ctx, HINGE_E_DEVICE, "hinge_overlap_run: a job's status slot was never written");
+                if (hits) hits[j] += o[2];
+                if (o[0] != OVL_ST_NONE) status[j] = (status[j] == OVL_ST_NONE ? 0 : status[j]) | o[0];
+                if (o[0] != OVL_ST_NONE && (o[0] & OVL_ST_OVERFLOW)) t->stats[5]++;
+                if (o[0] != OVL_ST_NONE && (o[0] & OVL_ST_TRUNCATED)) t->stats[6]++;
+                for (int c = 0; c < o[1]; c++) {
+                    const int* pk = o + OVL_HEAD + 4 * c;
+                    const int b = pk[0];
+                    const bool b_ok = b >= first && b < first + nr && b != J.a;
+                    const int blen = b_ok ? s->h_rlen[0][(size_t)b] : 0;
+                    OverlapCand oc;
+                    if (!b_ok || pk[1] < q.min_hits || pk[1] > o[2] || pk[2] < 1 || pk[2] >= J.alen + blen || pk[3] < 0 || pk[3] > J.alen - q.k ||
+                        !overlap_project(J.alen, blen, J.comp, pk[2], q.k, &oc.r.abpos, &oc.r.aepos, &oc.r.bbpos, &oc.r.bepos, &oc.diag))
+                        return fail(ctx, HINGE_E_DEVICE, "hinge_overlap_run: a candidate's slot was never written");
+                    oc.r.aread = J.a; oc.r.bread = b; oc.r.comp = J.comp; oc.r.tlen = 0; oc.r.trace_off = 0;
+                    oc.cnt = pk[1]; oc.d = pk[2]; oc.p = pk[3];
+                    t->cand.push_back(oc);
+                }
+            }
+        }
+    }
+    std::sort(t->cand.begin(), t->cand.end(), [](const OverlapCand& u, const OverlapCand& v) {
+        if (u.r.aread != v.r.aread) return u.r.aread < v.r.aread;
+        if (u.r.bread != v.r.bread) return u.r.bread < v.r.bread;
+        return u.r.comp < v.r.comp;
+    });
+    *n_out = (int64_t)t->cand.size();
+    return HINGE_OK;
+}
+
+int hinge_overlap_fetch(hinge_ctx* ctx, int64_t cap, hinge_cns_alignment* out, int32_t* count, int32_t* diag, int32_t* rep) {
+    if (!ctx || !ctx->ovl_st || cap < 0 || (cap > 0 && (!out || !count || !diag))) return fail(ctx, HINGE_E_ARG, "hinge_overlap_fetch: no hinge_overlap_run yet, or bad arguments");
+    const std::vector<OverlapCand>& c = ctx->ovl_st->cand;
+    if ((int64_t)c.size() > cap) return fail(ctx, HINGE_E_CAPACITY, "hinge_overlap_fetch: the output arrays must hold what hinge_overlap_run counted");
+    for (size_t x = 0; x < c.size(); x++) {
+        out[x] = c[x].r; count[x] = c[x].cnt; diag[x] = c[x].diag;
+        if (rep) { rep[2 * x] = c[x].d; rep[2 * x + 1] = c[x].p; }
+    }
+    return HINGE_OK;
+}
+
+int hinge_overlap_last_stats(hinge_ctx* ctx, int64_t* out) {
+    if (!ctx || !ctx->ovl_st || !out) return fail(ctx, HINGE_E_ARG, "hinge_overlap_last_stats: no hinge_overlap_run yet");
+    for (int k = 0; k < 8; k++) out[k] = ctx->ovl_st->stats[k];
+    return HINGE_OK;
+}
+
+}  // extern "C"

@@ -25,8 +25,8 @@
 // the power of two that holds the hit count, the window search's log2 steps, N picks, six cross-lane steps.  Nothing is read that
 // another wavefront writes; jobs are assigned by blockIdx; no atomics; the only barrier is that of the one-wavefront workgroup,
 // inside wavefront-uniform loops (the hit count nh is a sum of ballots: the same in every lane).
-// Not claimed: chaining, a second stretch of a read on one diagonal, hits inside a repeat of more than max_occ copies, read-vs-read
-// overlaps, more than one GPU.
+// Not claimed: chaining, a second stretch of a read on one diagonal, hits inside a repeat of more than max_occ copies, more
+// than one GPU.  (Read-vs-read overlaps: overlap_kernels.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

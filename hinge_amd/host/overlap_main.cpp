@@ -1,0 +1,239 @@
+// overlap  ==  `hinge overlap READ_DB OUT.las [--k K] [--step S] [--window W] [--max-occ C] [--list L] [--max-partners N] [--min-hits H] [--block-bases B]
+//                              [--min-len M] [--max-err E] [--tspace T] [--band W] [--band-max W]`
+// Not a program of the reference: it stands where the reference's run script calls DALIGNER (HPC.daligner + LAsort / LAmerge) on the
+// read DB against itself to get the read-vs-read .las that `hinge filter` opens.  The candidates - "reads a and b, strand, about this
+// diagonal" - are found by k-mer votes behind the C ABI (hinge_overlap_run, include/hinge_hip.h) and aligned by hinge_trace_local,
+// both on the GPU; this file reads the DB, makes the candidate set symmetric, filters the records and writes the .las.
+//   candidates  from all blocks; for every (a, b, comp) without its mirror, (b, a, comp) along the mirrored diagonal is added
+//   alignment   in chunks of A reads (both DB slots hold the read DB; --band / --band-max and the scratch budget are the library's):
+//               of every pair the candidate with aread < bread through hinge_trace_local; the pair's other record is the same
+//               stretch with the end points swapped, aligned between them by hinge_trace_run - both records cover the same bases
+//   filter      a record stays with both aligned lengths >= M (1000) and diffs / (aepos - abpos) <= E (0.30)
+//   pairs       a pair is written only if both of its directed records stay
+//   output      LAsort order (aread, bread, comp, abpos); trace values one byte up to tspace 125, as paf2las writes them
+#include "host_common.h"
+
+#include <unordered_set>
+
+using namespace hh;
+
+static void usage() {
+    fprintf(stderr, "usage: overlap <read db> <out.las> [--k K] [--step S] [--window W] [--max-occ C] [--list L] [--max-partners N] [--min-hits H] [--block-bases B]\n"
+                    "               [--min-len M] [--max-err E] [--tspace T] [--band W] [--band-max W]\n"
+                    "       read-vs-read overlaps of <read db> by k-mer votes and banded local alignment, as the .las `hinge filter` reads\n");
+}
+
+// both reads whole along the record-frame diagonal (bbpos - abpos), clamped to both; the rule of overlap_project (overlap_kernels.h)
+static bool along(int alen, int blen, long long diag, int k, hinge_cns_alignment& r) {
+    const long long ab = std::max(0ll, -diag), ae = std::min<long long>(alen, blen - diag);
+    if (ae - ab < k) return false;
+    r.abpos = (int)ab; r.aepos = (int)ae; r.bbpos = (int)(ab + diag); r.bepos = (int)(ae + diag);
+    return true;
+}
+
+static inline uint64_t pair_key(int a, int b, int comp) { return ((uint64_t)(uint32_t)a << 33) | ((uint64_t)(uint32_t)b << 1) | (uint64_t)(comp & 1); }
+
+int main(int argc, char* argv[]) {
+    std::vector<std::string> pos;
+    hinge_overlap_params prm;
+    memset(&prm, 0, sizeof(prm));                   // the library's defaults (15, 2, 256, 64, 4096, 64, 6, 16 Mi)
+    int min_len = 1000, tspace = 100, band = 0, band_max = 0;
+    double max_err = 0.30;
+    for (int i = 1; i < argc; i++) {
+        const std::string a = argv[i];
+        auto text = [&](const char* name) -> const char* {
+            if (i + 1 >= argc) { fprintf(stderr, "overlap: %s needs a value\n", name); usage(); exit(1); }
+            return argv[++i];
+        };
+        auto val = [&](const char* name) -> long long {
+            const long long v = atoll(text(name));
+            if (v < 1) { fprintf(stderr, "overlap: %s needs a positive number\n", name); usage(); exit(1); }
+            return v;
+        };
+        if (a == "--k") prm.k = (int32_t)val("--k");
+        else if (a == "--step") prm.step = (int32_t)val("--step");
+        else if (a == "--window") prm.window = (int32_t)val("--window");
+        else if (a == "--max-occ") prm.max_occ = (int32_t)val("--max-occ");
+        else if (a == "--list") prm.list = (int32_t)val("--list");
+        else if (a == "--max-partners") prm.max_partners = (int32_t)val("--max-partners");
+        else if (a == "--min-hits") prm.min_hits = (int32_t)val("--min-hits");
+        else if (a == "--block-bases") prm.block_bases = (int64_t)val("--block-bases");
+        else if (a == "--min-len") min_len = (int)val("--min-len");
+        else if (a == "--tspace") tspace = (int)val("--tspace");
+        else if (a == "--band") band = (int)val("--band");
+        else if (a == "--band-max") band_max = (int)val("--band-max");
+        else if (a == "--max-err") {
+            char* e = nullptr;
+            const char* t = text("--max-err");
+            max_err = strtod(t, &e);
+            if (e == t || *e || !(max_err >= 0.0 && max_err <= 1.0)) { fprintf(stderr, "overlap: --max-err needs a number in [0, 1]\n"); usage(); return 1; }
+        }
+        else if (a.size() > 2 && a[0] == '-' && a[1] == '-') { fprintf(stderr, "overlap: unknown option %s\n", a.c_str()); usage(); return 1; }
+        else pos.push_back(a);
+    }
+    if (pos.size() != 2 || tspace > 32767) { usage(); return 1; }
+    PhaseTimer tm("overlap");
+    CtxInit gpu;
+    gpu.start();
+    ReadDB db;
+    if (db.open(pos[0]) != 0) { fprintf(stderr, "overlap: Could not open database\n"); quit(1); }
+    Mapped bps;
+    const bool has = bps.open(db.dir + "/." + db.root + ".bps");
+    if (!has && !db.rlen.empty()) { fprintf(stderr, "overlap: cannot read the .bps file of the database\n"); quit(1); }
+    const int n_reads = (int)db.rlen.size();
+    tm.mark("ingest");
+    if (gpu.join() != HINGE_OK) { fprintf(stderr, "overlap: no usable GPU (%s)\n", gpu.ctx ? hinge_last_error(gpu.ctx) : "hinge_ctx_create failed"); quit(2); }
+    hinge_ctx* ctx = gpu.ctx;
+    auto die = [&](const char* what) { fprintf(stderr, "overlap: %s: %s\n", what, hinge_last_error(ctx)); quit(2); };
+    for (int which = 0; which < 2; which++)         // both slots: hinge_trace_local aligns reads to reads
+        if (hinge_consensus_set_db(ctx, which, n_reads, db.rlen.data(), db.boff.data(), bps.p, (int64_t)bps.n) != HINGE_OK) die("read DB");
+    tm.mark("H2D bases");
+
+    // ---- the candidates, made symmetric ------------------------------------------------------------------------------------------
+    std::vector<int32_t> jstatus((size_t)std::max(2 * n_reads, 2));
+    int64_t n_cand = 0;
+    if (hinge_overlap_run(ctx, &prm, jstatus.data(), nullptr, &n_cand) != HINGE_OK) die("votes");
+    std::vector<hinge_cns_alignment> cand((size_t)std::max<int64_t>(n_cand, 1));
+    std::vector<int32_t> count((size_t)std::max<int64_t>(n_cand, 1)), diag((size_t)std::max<int64_t>(n_cand, 1));
+    if (hinge_overlap_fetch(ctx, n_cand, cand.data(), count.data(), diag.data(), nullptr) != HINGE_OK) die("votes");
+    cand.resize((size_t)n_cand);
+    int64_t ost[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    (void)hinge_overlap_last_stats(ctx, ost);
+    tm.mark("index + votes");
+    const int k = prm.k ? prm.k : (getenv("HINGE_OVERLAP_K") && *getenv("HINGE_OVERLAP_K") ? atoi(getenv("HINGE_OVERLAP_K")) : 15);
+    int64_t mirrored = 0;
+    {
+        std::unordered_set<uint64_t> have;
+        have.reserve((size_t)n_cand * 2 + 16);
+        for (const hinge_cns_alignment& r : cand) have.insert(pair_key(r.aread, r.bread, r.comp));
+        for (int64_t x = 0; x < n_cand; x++) {
+            const hinge_cns_alignment r = cand[(size_t)x];
+            if (have.count(pair_key(r.bread, r.aread, r.comp))) continue;
+            const int alen = db.rlen[(size_t)r.aread], blen = db.rlen[(size_t)r.bread];
+            const long long md = r.comp ? (long long)alen - blen + diag[(size_t)x] : -(long long)diag[(size_t)x];      // the mirrored diagonal
+            hinge_cns_alignment m;
+            m.aread = r.bread; m.bread = r.aread; m.comp = r.comp; m.tlen = 0; m.trace_off = 0;
+            if (!along(blen, alen, md, k, m)) continue;
+            cand.push_back(m);
+            mirrored++;
+        }
+        std::sort(cand.begin(), cand.end(), [](const hinge_cns_alignment& x, const hinge_cns_alignment& y) {
+            if (x.aread != y.aread) return x.aread < y.aread;
+            if (x.bread != y.bread) return x.bread < y.bread;
+            return x.comp < y.comp;
+        });
+    }
+    const int64_t n = (int64_t)cand.size();
+
+    // ---- aligned in chunks of A reads.  The directed candidates with aread < bread go through hinge_trace_local; a record stays with
+    //      both lengths >= M and diffs / (aepos - abpos) <= E.  Its pair's other record is the SAME stretch seen from read b: the end
+    //      points swapped (in the comp frame: counted from the other end), aligned between them by hinge_trace_run - so both records of
+    //      a pair cover the same bases, as the two records DALIGNER writes for one alignment do (`hinge draft` finds an edge's record by
+    //      the sum of its two lengths, whichever direction the layout took it from) ----------------------------------------------------------
+    int room = 50;                                  // no widened box reaches further than this beyond the given one (HINGE_TRACE_EXTEND)
+    {
+        const char* g = getenv("HINGE_TRACE_EXTEND");
+        if (g && *g) room = std::max(atoi(g), 0);
+    }
+    const int64_t chunk_records = 1 << 18;
+    struct Kept { hinge_cns_alignment r; int32_t diffs; int64_t toff; };
+    std::vector<Kept> kept;
+    std::vector<uint16_t> ktrace;
+    int64_t aligned = 0, asym = 0;
+    auto by_key = [](const hinge_cns_alignment& x, const hinge_cns_alignment& y) {
+        if (x.aread != y.aread) return x.aread < y.aread;
+        if (x.bread != y.bread) return x.bread < y.bread;
+        return x.comp < y.comp;
+    };
+    // one round: `in` (sorted by A read) through hinge_trace_local (local) or hinge_trace_run; what stays goes to `kept`, the rest is counted
+    auto align_round = [&](const std::vector<hinge_cns_alignment>& in, bool local, int64_t& dropped) {
+        std::vector<hinge_cns_alignment> out;
+        std::vector<uint16_t> trace;
+        std::vector<int32_t> diffs, status, score;
+        const int64_t n_in = (int64_t)in.size();
+        const int rm = local ? room : 0;
+        for (int64_t x0 = 0; x0 < n_in;) {
+            int64_t x1 = std::min(n_in, x0 + chunk_records);
+            while (x1 < n_in && in[(size_t)x1].aread == in[(size_t)x1 - 1].aread) x1++;        // whole A reads
+            const int64_t m = x1 - x0;
+            int64_t cap = 0;
+            for (int64_t x = x0; x < x1; x++) cap += 2 * (int64_t)((in[(size_t)x].aepos + rm - 1) / tspace - std::max(in[(size_t)x].abpos - rm, 0) / tspace + 1);
+            out.resize((size_t)m); trace.resize((size_t)std::max<int64_t>(cap, 1)); diffs.resize((size_t)m); status.resize((size_t)(2 * m)); score.resize((size_t)m);
+            int64_t n_trace = 0;
+            const int rc = local ? hinge_trace_local(ctx, m, in.data() + x0, tspace, band, band_max, nullptr, out.data(), trace.data(), cap, &n_trace, diffs.data(), status.data(), score.data())
+                                 : hinge_trace_run(ctx, m, in.data() + x0, tspace, band, band_max, out.data(), trace.data(), cap, &n_trace, diffs.data(), status.data());
+            if (rc != HINGE_OK) die("trace");
+            for (int64_t x = 0; x < m; x++) {
+                const hinge_cns_alignment& r = out[(size_t)x];
+                if (status[(size_t)(2 * x)] != 0) { dropped++; continue; }
+                aligned++;
+                if (r.aepos - r.abpos < min_len || r.bepos - r.bbpos < min_len || (double)diffs[(size_t)x] > max_err * (double)(r.aepos - r.abpos)) { dropped++; continue; }
+                kept.push_back(Kept{r, diffs[(size_t)x], (int64_t)ktrace.size()});
+                ktrace.insert(ktrace.end(), trace.begin() + r.trace_off, trace.begin() + r.trace_off + r.tlen);
+            }
+            x0 = x1;
+        }
+    };
+    std::vector<hinge_cns_alignment> first;
+    for (const hinge_cns_alignment& r : cand)
+        if (r.aread < r.bread) first.push_back(r);
+    int64_t unaligned = 0;
+    align_round(first, true, unaligned);
+    std::vector<hinge_cns_alignment> second;
+    second.reserve(kept.size());
+    for (const Kept& q : kept) {
+        const hinge_cns_alignment& r = q.r;
+        const int alen = db.rlen[(size_t)r.aread], blen = db.rlen[(size_t)r.bread];
+        hinge_cns_alignment m;
+        m.aread = r.bread; m.bread = r.aread; m.comp = r.comp; m.tlen = 0; m.trace_off = 0;
+        if (!r.comp) { m.abpos = r.bbpos; m.aepos = r.bepos; m.bbpos = r.abpos; m.bepos = r.aepos; }
+        else { m.abpos = blen - r.bepos; m.aepos = blen - r.bbpos; m.bbpos = alen - r.aepos; m.bepos = alen - r.abpos; }
+        second.push_back(m);
+    }
+    std::sort(second.begin(), second.end(), by_key);
+    align_round(second, false, asym);
+    std::sort(kept.begin(), kept.end(), [&](const Kept& x, const Kept& y) { return by_key(x.r, y.r); });
+    tm.mark("align + trace");
+
+    // ---- a pair only with both of its directed records; the .las in LAsort order (aread, bread, comp, abpos: one record per key) ---------
+    std::unordered_set<uint64_t> stay;
+    stay.reserve(kept.size() * 2 + 16);
+    for (const Kept& q : kept) stay.insert(pair_key(q.r.aread, q.r.bread, q.r.comp));
+    int64_t written = 0;
+    for (const Kept& q : kept) written += stay.count(pair_key(q.r.bread, q.r.aread, q.r.comp)) ? 1 : 0;
+    FILE* fo = fopen(pos[1].c_str(), "wb");
+    if (!fo) { fprintf(stderr, "overlap: cannot write %s\n", pos[1].c_str()); quit(1); }
+    const int32_t ts32 = tspace;
+    fwrite(&written, 8, 1, fo);
+    fwrite(&ts32, 4, 1, fo);
+    const int tbytes = tspace <= 125 ? 1 : 2;
+    std::vector<uint8_t> tb;
+    std::vector<char> has_record((size_t)std::max(n_reads, 1), 0);
+    for (const Kept& q : kept) {
+        if (!stay.count(pair_key(q.r.bread, q.r.aread, q.r.comp))) continue;
+        const hinge_cns_alignment& r = q.r;
+        has_record[(size_t)r.aread] = 1;
+        uint8_t rec[40];
+        memset(rec, 0, sizeof(rec));
+        const int32_t v[9] = {r.tlen, q.diffs, r.abpos, r.bbpos, r.aepos, r.bepos, r.comp ? 1 : 0, r.aread, r.bread};
+        memcpy(rec, v, 36);
+        fwrite(rec, 40, 1, fo);
+        tb.resize((size_t)r.tlen * (size_t)tbytes);
+        for (int t = 0; t < r.tlen; t++) {
+            const uint16_t val = ktrace[(size_t)q.toff + (size_t)t];
+            if (tbytes == 1) tb[(size_t)t] = (uint8_t)val;
+            else { tb[(size_t)2 * t] = (uint8_t)(val & 0xff); tb[(size_t)2 * t + 1] = (uint8_t)(val >> 8); }
+        }
+        if (!tb.empty()) fwrite(tb.data(), 1, tb.size(), fo);
+    }
+    if (fclose(fo) != 0) { fprintf(stderr, "overlap: cannot write %s\n", pos[1].c_str()); quit(1); }
+    int64_t lonely = 0;
+    for (int r = 0; r < n_reads; r++) lonely += !has_record[(size_t)r];
+    printf("overlap: %d reads, %lld job(s) in %lld batch(es) over %lld block(s); %lld candidates, %lld mirrored, %lld aligned, %lld written, %lld dropped for asymmetry; index %lld entries (%lld codes dropped by max-occ)\n",
+           n_reads, (long long)ost[0], (long long)ost[1], (long long)ost[2], (long long)n_cand, (long long)mirrored, (long long)aligned, (long long)written, (long long)asym, (long long)ost[3],
+           (long long)ost[4]);
+    fprintf(stderr, "overlap: %lld job(s) with dropped hits (OVERFLOW), %lld job(s) with dropped partners (TRUNCATED), %lld read(s) without any overlap\n", (long long)ost[5], (long long)ost[6],
+            (long long)lonely);
+    tm.mark("write");
+    return finish(ctx, tm, 0);
+}

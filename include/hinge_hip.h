@@ -536,7 +536,7 @@ int hinge_trace_last_stats(hinge_ctx* ctx, int64_t* out);
  * draft of 2^31 or more bases, cap too small.  HINGE_E_DEVICE: a failed allocation, or an output slot the kernel did not write
  * (the outputs are poisoned before every launch).  Jobs run in batches under HINGE_SEED_SCRATCH_MB (256) of job and result slots.
  * Not claimed: chaining; a second stretch of one read on the same diagonal; hits from a repeat of more than max_occ copies;
- * read-vs-read overlaps; more than one GPU.                                                                                   */
+ * more than one GPU.  (Read-vs-read overlaps: hinge overlap below.)                                                           */
 typedef struct hinge_seed_params {
     int32_t k, step, window, max_occ, list, max_placements, min_hits;
 } hinge_seed_params;
@@ -549,6 +549,59 @@ int hinge_seed_db_reads(hinge_ctx* ctx, int64_t* n_reads);
 /* Of the last hinge_seed_run: out[0] jobs, [1] batches, [2] index entries, [3] codes dropped by max_occ, [4] OVERFLOW jobs, [5] reads
  * without placement, [6] microseconds of the index (host build, upload), [7] 0. */
 int hinge_seed_last_stats(hinge_ctx* ctx, int64_t* out);
+
+/* ---- hinge overlap -----------------------------------------------------------------------------------------
+ * Read-vs-read overlap candidates by k-mer votes: "reads a and b, strand s, about this diagonal", for hinge_trace_local to
+ * align.  Not a program of the reference (its run script calls DALIGNER there).  BOTH DBs of hinge_consensus_set_db must be the
+ * read DB (so hinge_trace_local is used as it is).
+ *   blocks     the reads in blocks of consecutive ids of at most block_bases bases each (a longer read: alone).  Per block (host,
+ *              one resident at a time) the index of hinge seed over the block's reads: every k-mer at every position, none
+ *              across two reads, as (code, gpos) sorted by both; a code with more than max_occ entries IN THE BLOCK has none
+ *   job        one per (read a, strand, block); Q = read a in the strand's frame, alen its length; the targets are forward.
+ *              Sampled positions p as in hinge seed.  Every entry of p's code is a hit (b, d, p): b = the read holding gpos,
+ *              d = (gpos - off[b]) - p + alen.  Hits with b == a are discarded before the list is cut (they take no slot); the
+ *              rest is enumerated by p then gpos; hits beyond `list` are dropped and the job is flagged OVERFLOW
+ *   groups     hits sorted by (b, d, p); cnt[i] = elements j >= i of the same b with d[j] < d[i] + window.  Per b the pick is
+ *              the largest cnt, of equal ones the smallest i; its representative is element i + cnt[i] / 2.  A pick of
+ *              cnt >= min_hits is a candidate (b, cnt, d, p): ONE per (a, b, strand)
+ *   partners   a job's candidates in ascending b, the first max_partners; further ones are dropped (TRUNCATED)
+ *   record     A = read a forward, B = read b in the comp frame (comp = the job's strand): both reads whole along the
+ *              representative's diagonal, clamped to both (overlap_project, overlap_kernels.h); diag = bbpos - abpos
+ * params: 0 = the default - HINGE_OVERLAP_K / _STEP / _WINDOW / _MAX_OCC / _LIST / _MAX_PARTNERS / _MIN_HITS / _BLOCK_BASES, else
+ *   k 15 (8..16), step 2, window 256 (a power of two, 16..65536), max_occ HINGE_OVERLAP_MAX_OCC = 64 (1..256), list 4096 (a
+ *   power of two, 64..8192: 16 bytes of LDS per slot, and a workgroup may take the CU's 160 KiB), max_partners 64 (1..4096),
+ *   min_hits HINGE_OVERLAP_MIN_HITS = 6, block_bases 16 Mi (1..2^31-1).  NULL = all defaults.
+ *   min_hits: the largest group count over all pairs of 400 unrelated reads of 7 128 random bases (both strands, one block,
+ *   k 15, step 2, window 256, max_occ 64) was 4 (7 062 pairs with a hit: 6 618 x 1, 417 x 2, 26 x 3, 1 x 4 - a chance match of
+ *   13 + 2 c bases in a row gives c hits on one diagonal, a quarter as often per two bases more); by the rule of hinge seed
+ *   (the largest count of unrelated pairs, plus half, rounded up) that gives 6, where the starting value 3 would have let 27
+ *   unrelated pairs through (tools/overlap_measure.py min-hits).  Against it: the generator's pairs sharing >= 2 000 genome bases
+ *   at 10 % errors per read have 17 hits at the least, 77 in the median (tools/overlap_measure.py recall).
+ *   max_occ: a k-mer that is unique in the genome has at most as many entries as reads cover it - about 30 per block at 30x with
+ *   error-free reads (Poisson: beyond 64 with p < 1e-6), a two-copy repeat's 60 - so 64 keeps both and drops what has three
+ *   copies or more; at 10 % errors per read the largest code of a 30x set had 16 entries and none was dropped
+ *   (tools/overlap_measure.py max-occ).
+ * Outputs: status[2 n_reads] = per (read, strand) over all blocks 1 NONE (shorter than k, or no group of min_hits), else the bits
+ *   2 OVERFLOW and 4 TRUNCATED (0 = neither); *n_out = candidates found.  hinge_overlap_fetch copies them - out / count / diag
+ *   [cap], cap >= *n_out - sorted by (aread, bread, comp), tlen 0, trace_off 0: what hinge_trace_local reads.  hits[2 n_reads] (or
+ *   NULL): the hits a (read, strand) kept, summed over the blocks; rep[2 cap] (or NULL): a candidate's (d, p) as the kernel gave it.
+ * HINGE_E_ARG: parameters outside their range; the two DBs differ.  HINGE_E_CAPACITY (before any launch): a read of 2^20 or
+ *   more bases (the hit key: b in 23 bits, d in 21, p in 20), more than 2^23 - 1 reads or 2^31 - 1 bases in a block (blocks are
+ *   cut so that neither happens), cap too small.  HINGE_E_DEVICE: a failed allocation, or an output slot the kernel did not
+ *   write (the outputs are poisoned before every launch).  Jobs run in batches under HINGE_OVERLAP_SCRATCH_MB (256).
+ * Not claimed: chaining; a second stretch of the same pair; k-mers of more than max_occ copies per block; reads of 2^20 or more
+ *   bases; more than one GPU; parity with DALIGNER's record set; index build speed (host, reported only).                       */
+typedef struct hinge_overlap_params {
+    int32_t k, step, window, max_occ, list, max_partners, min_hits, pad;
+    int64_t block_bases;
+} hinge_overlap_params;
+#define HINGE_OVERLAP_MIN_HITS 6
+#define HINGE_OVERLAP_MAX_OCC 64
+int hinge_overlap_run(hinge_ctx* ctx, const hinge_overlap_params* params, int32_t* status, int32_t* hits, int64_t* n_out);
+int hinge_overlap_fetch(hinge_ctx* ctx, int64_t cap, hinge_cns_alignment* out, int32_t* count, int32_t* diag, int32_t* rep);
+/* Of the last hinge_overlap_run: out[0] jobs (read, strand, block), [1] batches, [2] blocks, [3] index entries (all blocks), [4] codes
+ * dropped by max_occ, [5] OVERFLOW jobs, [6] TRUNCATED jobs, [7] microseconds of the indexes (host build, upload). */
+int hinge_overlap_last_stats(hinge_ctx* ctx, int64_t* out);
 
 /* Per-kernel timing with HIP events recorded around every launch on the context's stream.
  * enable(max_launches > 0) starts a fresh recording; report() synchronises and returns total ms and

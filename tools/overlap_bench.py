@@ -1,0 +1,122 @@
+#!/usr/bin/env python
+"""`hinge overlap` at bench size: the reads of hinge_amd/synth_consensus.py "cns_bench" (4 contigs of ~1.1 Mb at 30x: 18.8 k reads,
+E. coli size) against themselves through hinge_overlap_run, then hinge_trace_local on the candidates.  One JSON line; every figure
+sits in "figures" as {"value": ..., "measured": "gpu" | "host" | "not measured"}:
+  index_ms (host build and upload of every block's index), k_overlap_vote_ms (HIP events, hinge_profile_*), candidates_per_s (by the
+  kernel's time), trace_local_ms and its records on the first --align candidates (0 = all), records_written (the executable, with
+  --cli), recall: the generator's pairs sharing >= 2 000 contig bases (from the reads' longest records on the contigs they were cut
+  from) that are candidates after the mirror step.
+There is no reference program for this step here (DALIGNER is not part of the reference tree): no speed-up factor is claimed.
+
+    python tools/overlap_bench.py [--config cns_bench] [--steps 2] [--align 200000] [--cli] [--keep DIR]
+"""
+import argparse
+import json
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def truth_pairs(d, min_shared):
+    """{(a, b, comp)} of ordered read pairs whose longest records lie on one contig and share >= min_shared of its bases."""
+    import numpy as np
+    best = {}
+    for q in d.rec:
+        b, ln = int(q["bread"]), int(q["aepos"]) - int(q["abpos"])
+        if b not in best or ln > best[b][0]:
+            best[b] = (ln, int(q["aread"]), int(q["abpos"]), int(q["aepos"]), int(q["flags"]) & 1)
+    ids = np.asarray(sorted(best), np.int64)
+    c = np.asarray([best[b][1] for b in ids]); s = np.asarray([best[b][2] for b in ids]); e = np.asarray([best[b][3] for b in ids]); st = np.asarray([best[b][4] for b in ids])
+    out = set()
+    order = np.lexsort((s, c))
+    ids, c, s, e, st = ids[order], c[order], s[order], e[order], st[order]
+    key = s + (c.astype(np.int64) << 40)
+    for i in range(len(ids)):
+        j1 = int(np.searchsorted(key, e[i] + (int(c[i]) << 40), side="left"))
+        for j in range(i + 1, j1):
+            if min(e[i], e[j]) - s[j] >= min_shared:
+                comp = int(st[i] != st[j])
+                out.add((int(ids[i]), int(ids[j]), comp)); out.add((int(ids[j]), int(ids[i]), comp))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="cns_bench")
+    ap.add_argument("--steps", type=int, default=2)
+    ap.add_argument("--align", type=int, default=200000)
+    ap.add_argument("--cli", action="store_true")
+    ap.add_argument("--keep", default="")
+    args = ap.parse_args()
+    import numpy as np
+    import consensus_common as cc
+    import overlap_common as oc
+    from hinge_amd import capi
+    wd = args.keep or tempfile.mkdtemp(prefix="hinge_overlap_")
+    os.makedirs(wd, exist_ok=True)
+    d = cc.make(args.config, wd)
+    rlen = np.asarray([len(x) for x in d.reads], np.int64)
+    fig = {}
+
+    def put(name, value, how):
+        fig[name] = {"value": value, "measured": how}
+    out = {"config": args.config, "reads": len(d.reads), "read_bases": int(rlen.sum()), "reference_program": None,
+           "note": "no reference program for this step on this machine (DALIGNER is an empty submodule of the reference): no speed-up factor", "figures": fig}
+    ctx = capi.Context(0)
+    capi.Consensus(ctx, os.path.join(wd, "reads"), os.path.join(wd, "reads"))
+    t = time.time()
+    pl, count, diag, rep, status, hits = ctx.overlap_run()                               # warm-up (allocations)
+    out["first_call_s"] = round(time.time() - t, 3)
+    out["stats"] = ctx.overlap_stats()
+    out["status"] = {str(s): int(c) for s, c in zip(*np.unique(status, return_counts=True))}
+    ctx.profile_enable(4096)
+    t = time.time()
+    index_us = []
+    for _ in range(args.steps):
+        ctx.overlap_run()
+        index_us.append(ctx.overlap_stats()["index_us"])
+    call_ms = (time.time() - t) * 1e3 / args.steps
+    prof = ctx.profile_report()
+    kernel_ms = prof["k_overlap_vote"][0] / args.steps
+    put("index_ms", round(float(np.mean(index_us)) / 1e3, 3), "host")
+    put("k_overlap_vote_ms", round(kernel_ms, 3), "gpu")
+    put("run_call_ms", round(call_ms, 3), "host")
+    put("candidates", int(len(pl)), "gpu")
+    put("candidates_per_s", round(len(pl) / (kernel_ms * 1e-3)) if kernel_ms else None, "gpu")
+    put("largest_hits_kept", int(hits.max()) if hits.size else 0, "gpu")
+    # ---- recall, candidate level, after the mirror step ------------------------------------------------------------------------------------
+    want = truth_pairs(d, 2000)
+    sym, sdg, added = oc.symmetrise([tuple(r) for r in pl.tolist()], diag.tolist(), rlen)
+    got = {tuple(r[:3]) for r in sym}
+    put("recall_pairs_2000", {"pairs": len(want), "candidates_of_them": len(want & got), "recall": len(want & got) / max(len(want), 1), "mirrored": added}, "gpu")
+    # ---- hinge_trace_local on the candidates ----------------------------------------------------------------------------------------------------
+    sym = np.asarray(sym, np.int64).reshape(-1, 7)
+    part = sym if args.align <= 0 else sym[:args.align]
+    ctx.profile_enable(65536)
+    t = time.time()
+    alns, trace, diffs, st, score = ctx.trace_local(part, 100)
+    wall = time.time() - t
+    prof = ctx.profile_report()
+    put("trace_local_ms", {"kernels_ms": round(sum(v[0] for k, v in prof.items() if k.startswith("k_trace")), 3), "call_s": round(wall, 3), "candidates": int(len(part)),
+                           "of": int(len(sym)), "records": int((st[:, 0] == 0).sum())}, "gpu")
+    if args.cli:
+        t = time.time()
+        r = subprocess.run([os.path.join(ROOT, "hinge_amd", "bin", "hinge"), "overlap", "reads", "reads.las"], cwd=wd, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        put("records_written", {"summary": r.stdout.decode().strip(), "stderr": r.stderr.decode().strip().splitlines()[-1:], "wall_s": round(time.time() - t, 3)}, "gpu")
+    else:
+        put("records_written", None, "not measured")
+    print(json.dumps(out))
+    if not args.keep:
+        shutil.rmtree(wd, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main()
