@@ -125,6 +125,10 @@ SYMBOLS = [
     ("hinge_overlap_run", C.c_int, [_VP, _VP, _VP, _VP, C.POINTER(C.c_int64)]),
     ("hinge_overlap_fetch", C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, _VP]),
     ("hinge_overlap_last_stats", C.c_int, [_VP, _VP]),
+    ("hinge_index_build", C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("hinge_index_fetch", C.c_int, [_VP, C.c_int64, _VP, _VP, _VP]),
+    ("hinge_index_last_stats", C.c_int, [_VP, _VP]),
+    ("hinge_index_tile", C.c_int, []),
     ("hinge_profile_report", C.c_int, [_VP, _VP, _VP]),
     ("hinge_timer_start", C.c_int, [_VP]),
     ("hinge_timer_stop_ms", C.c_int, [_VP, C.POINTER(C.c_float)]),
@@ -625,7 +629,7 @@ class Context:
 
     def seed_stats(self) -> dict:
         """Of the last seed_run: jobs, batches, index entries, codes dropped by max_occ, OVERFLOW jobs, reads without placement, and
-        the microseconds the index took (host build, upload)."""
+        the microseconds the index took (whichever path built it: index_last_stats)."""
         st = np.zeros(8, np.int64)
         self._ck(self.lib.hinge_seed_last_stats(self.h, _ptr(st)))
         return dict(zip(("jobs", "batches", "entries", "dropped_codes", "overflow", "unplaced", "index_us"), [int(v) for v in st[:7]]))
@@ -656,10 +660,31 @@ class Context:
 
     def overlap_stats(self) -> dict:
         """Of the last overlap_run: jobs (read, strand, block), batches, blocks, index entries, codes dropped by max_occ, OVERFLOW
-        jobs, TRUNCATED jobs, and the microseconds the indexes took (host build, upload)."""
+        jobs, TRUNCATED jobs, and the microseconds the indexes took (whichever path built them: index_last_stats)."""
         st = np.zeros(8, np.int64)
         self._ck(self.lib.hinge_overlap_last_stats(self.h, _ptr(st)))
         return dict(zip(("jobs", "batches", "blocks", "entries", "dropped_codes", "overflow", "truncated", "index_us"), [int(v) for v in st[:8]]))
+
+    def index_build(self, first: int, n_seqs: int, k: int, max_occ: int, where: int = -1):
+        """hinge_index_build + hinge_index_fetch: the k-mer index of sequences [first, first + n_seqs) of DB 0 of Consensus(ctx, ...),
+        as hinge seed and hinge overlap use it.  where: 1 device, 0 host, -1 HINGE_INDEX_DEVICE.  Returns (codes uint32 [m], gpos
+        int32 [m], off int64 [n_seqs + 1], dropped_codes) and leaves the call's figures in index_last_stats()."""
+        m, dropped = C.c_int64(0), C.c_int64(0)
+        self._ck(self.lib.hinge_index_build(self.h, int(first), int(n_seqs), int(k), int(max_occ), int(where), C.byref(m), C.byref(dropped)))
+        m = int(m.value)
+        codes = np.zeros(max(m, 1), dtype=np.uint32)
+        gpos = np.zeros(max(m, 1), dtype=np.int32)
+        off = np.zeros(int(n_seqs) + 1, dtype=np.int64)
+        self._ck(self.lib.hinge_index_fetch(self.h, m, _ptr(codes), _ptr(gpos), _ptr(off)))
+        return codes[:m], gpos[:m], off, int(dropped.value)
+
+    def index_last_stats(self) -> dict:
+        """Of the last index_build / seed_run / overlap_run, summed over its blocks: entries before the filter, entries kept, codes
+        dropped, ranges built on the device, ranges built on the host, sort passes of the last device build, microseconds, scratch
+        bytes in use."""
+        st = np.zeros(8, np.int64)
+        self._ck(self.lib.hinge_index_last_stats(self.h, _ptr(st)))
+        return dict(zip(("entries", "kept", "dropped_codes", "device_builds", "host_builds", "passes", "index_us", "scratch_bytes"), [int(v) for v in st[:8]]))
 
     def profile_enable(self, max_launches: int):
         self._ck(self.lib.hinge_profile_enable(self.h, int(max_launches)))

@@ -21,6 +21,7 @@
 #include "seed_kernels.h"
 #include "seed_index.h"
 #include "overlap_kernels.h"
+#include "index_kernels.h"
 
 using namespace hinge;
 
@@ -161,6 +162,7 @@ struct hinge_ctx {
     struct TraceState* trace_st = nullptr;   // `hinge paf2las` (trace_capi.inc)
     struct SeedState* seed_st = nullptr;     // `hinge seed` (seed_capi.inc)
     struct OverlapState* ovl_st = nullptr;   // `hinge overlap` (overlap_capi.inc)
+    struct IndexState* idx_st = nullptr;     // the k-mer index of both (index_capi.inc)
     void* comm = nullptr;               // ncclComm_t of this context among the contexts of its process (comm_capi.inc)
     int comm_rank = -1, comm_size = 0;
     DevBuf comm_stage;                  // all-gathered mask rows [comm_size + 1][S][2]
@@ -170,16 +172,19 @@ struct hinge_ctx {
 };
 
 enum KernelId { KID_STATS = 0, KID_MEDIAN, KID_MASK_ANNOTATE, KID_MASK_FALLBACK, KID_HINGE_COUNT, KID_HINGE_CALL, KID_HINGE_EXACT, KID_COVERAGE_BINS, KID_TRIM_CLASSIFY,
-                KID_PILEUP_FACTS, KID_MATCHING_POSITION, KID_SELECT_EDGES, KID_SPEC_PREDICT, KID_MASK_FINAL, KID_CNS_REALIGN, KID_CNS_COLUMNS, KID_CNS_VOTE, KID_CNS_CALL, KID_DRAFT_ALIGN, KID_DRAFT_CNS, KID_DRAFT_ALIGN_LONG, KID_DRAFT_CNS_DEEP, KID_MASK_LONG, KID_TRACE_FILL, KID_TRACE_WALK, KID_TRACE_CLIP, KID_TRACE_FILL_LOCAL, KID_TRACE_WALK_LOCAL, KID_SEED_VOTE, KID_EXACT_BEGIN, KID_OVERLAP_VOTE, KID_COUNT };
+                KID_PILEUP_FACTS, KID_MATCHING_POSITION, KID_SELECT_EDGES, KID_SPEC_PREDICT, KID_MASK_FINAL, KID_CNS_REALIGN, KID_CNS_COLUMNS, KID_CNS_VOTE, KID_CNS_CALL, KID_DRAFT_ALIGN, KID_DRAFT_CNS, KID_DRAFT_ALIGN_LONG, KID_DRAFT_CNS_DEEP, KID_MASK_LONG, KID_TRACE_FILL, KID_TRACE_WALK, KID_TRACE_CLIP, KID_TRACE_FILL_LOCAL, KID_TRACE_WALK_LOCAL, KID_SEED_VOTE, KID_EXACT_BEGIN, KID_OVERLAP_VOTE, KID_INDEX_EXTRACT, KID_INDEX_HIST,
+                KID_INDEX_SCAN, KID_INDEX_SCATTER, KID_INDEX_FLAG, KID_INDEX_COMPACT, KID_COUNT };
 static const char* const KERNEL_NAMES[KID_COUNT] = {"k_cov_stats", "k_median_hist", "k_mask_annotate", "k_mask_annotate_fallback", "k_hinge_count", "k_hinge_call", "k_hinge_exact",
                                                      "k_coverage_bins", "k_trim_classify", "k_pileup_facts", "k_matching_position", "k_select_edges", "k_spec_predict",
-                                                     "k_mask_annotate_final", "k_cns_realign", "k_cns_columns", "k_cns_vote", "k_cns_call", "k_draft_align", "k_draft_cns", "k_draft_align_long", "k_draft_cns_deep", "k_mask_annotate_long", "k_trace_fill", "k_trace_walk", "k_trace_clip", "k_trace_fill_local", "k_trace_walk_local", "k_seed_vote", "k_exact_begin", "k_overlap_vote"};
+                                                     "k_mask_annotate_final", "k_cns_realign", "k_cns_columns", "k_cns_vote", "k_cns_call", "k_draft_align", "k_draft_cns", "k_draft_align_long", "k_draft_cns_deep", "k_mask_annotate_long", "k_trace_fill", "k_trace_walk", "k_trace_clip", "k_trace_fill_local", "k_trace_walk_local", "k_seed_vote", "k_exact_begin", "k_overlap_vote", "k_index_extract", "k_index_hist",
+                                                     "k_index_scan", "k_index_scatter", "k_index_flag", "k_index_compact"};
 
 struct ProfScope {
     hinge_ctx* c;
     bool on;
     ProfScope(hinge_ctx* ctx, int kid) : c(ctx), on(false) {
-        if (c->prof_on && ((c->prof_mask >> kid) & 1u) && c->prof_used + 2 <= c->prof_pool.size()) {
+        // (the mask has 32 bits: a kernel id of 32 or more gets events while no selection is in force)
+        if (c->prof_on && (kid < 32 ? ((c->prof_mask >> kid) & 1u) != 0u : c->prof_mask == 0xffffffffu) && c->prof_used + 2 <= c->prof_pool.size()) {
             on = true;
             c->prof_kid.push_back(kid);
             (void)hipEventRecord(c->prof_pool[c->prof_used], c->stream);
@@ -349,6 +354,7 @@ static void draft_release(hinge_ctx* ctx);
 static void trace_release(hinge_ctx* ctx);
 static void seed_release(hinge_ctx* ctx);
 static void overlap_release(hinge_ctx* ctx);
+static void index_release(hinge_ctx* ctx);
 static void comm_release(hinge_ctx* ctx);
 void hinge_ctx_destroy(hinge_ctx* ctx) {
     if (!ctx) return;
@@ -358,6 +364,7 @@ void hinge_ctx_destroy(hinge_ctx* ctx) {
     trace_release(ctx);
     seed_release(ctx);
     overlap_release(ctx);
+    index_release(ctx);
     comm_release(ctx);
     DevBuf* all[] = {&ctx->rlen, &ctx->qv_mask, &ctx->row_ptr, &ctx->a_span, &ctx->b_span, &ctx->b_flag, &ctx->mask_own, &ctx->mean_own,
                      &ctx->cmask, &ctx->rflags, &ctx->nbins0, &ctx->anno_buf, &ctx->anno_off, &ctx->anno_cnt, &ctx->hinge_flag,
@@ -2259,6 +2266,7 @@ int hinge_timer_stop_ms(hinge_ctx* ctx, float* ms) {
 #include "consensus_capi.inc"
 #include "draft_capi.inc"
 #include "trace_capi.inc"
+#include "index_capi.inc"
 #include "seed_capi.inc"
 #include "overlap_capi.inc"
 #include "comm_capi.inc"

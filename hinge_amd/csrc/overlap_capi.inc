@@ -1,6 +1,6 @@
 // C ABI of `hinge overlap` (include/hinge_hip.h, "hinge overlap").  Included by hinge_capi.hip.
-// Host work here: the parameters' defaults and ranges, the limits of the key packing, the target blocks and their k-mer indexes
-// (seed_index.h; built from the host copy of DB 0's bases that hinge_consensus_set_db keeps, one block resident at a time), the
+// Host work here: the parameters' defaults and ranges, the limits of the key packing, the target blocks and the calls of their k-mer
+// indexes (index_capi.inc: built on the device from the resident bases, or by seed_index.h on the host; one block resident at a time), the
 // jobs (two per read) in batches under the scratch budget against every block, a candidate's projection in the record's frame
 // (overlap_project) and the order of the result.  The kernel: overlap_kernels.h.
 
@@ -104,27 +104,19 @@ int hinge_overlap_run(hinge_ctx* ctx, const hinge_overlap_params* params, int32_
     const long long per_job = (long long)sizeof(OvlJob) + (long long)sizeof(int) * W;
     const int64_t per_batch = std::min<long long>(std::max<long long>(budget / per_job, 1), 1 << 20);
     std::vector<int> h_out;
+    std::vector<long long> ix_off;
     int rc;
+    index_stats_reset(ctx);
     for (int blk = 0; blk < n_blocks; blk++) {
-        // ---- the block's index, the entries up ----------------------------------------------------------------------------------------------------
-        const auto t0 = std::chrono::steady_clock::now();
+        // ---- the block's index (index_capi.inc): on the device from the resident bases, or on the host and up ----------------------------------------------------
         const int first = bfirst[(size_t)blk], nr = bfirst[(size_t)blk + 1] - first;
-        SeedIndex ix;
-        seed_build_index(s->h_bps0.data(), s->h_boff0.data() + first, s->h_rlen[0].data() + first, nr, q.k, q.max_occ, ix);
-        const size_t ne = ix.codes.size();
-        if ((rc = ensure(ctx, t->codes, sizeof(uint32_t) * std::max<size_t>(ne, 1)))) return rc;
-        if ((rc = ensure(ctx, t->gpos, sizeof(int32_t) * std::max<size_t>(ne, 1)))) return rc;
-        if ((rc = ensure(ctx, t->off, sizeof(long long) * ((size_t)nr + 1)))) return rc;
-        if (ne) {
-            CK(hipMemcpyAsync(t->codes.p, ix.codes.data(), sizeof(uint32_t) * ne, hipMemcpyHostToDevice, ctx->stream));
-            CK(hipMemcpyAsync(t->gpos.p, ix.gpos.data(), sizeof(int32_t) * ne, hipMemcpyHostToDevice, ctx->stream));
-        }
-        CK(hipMemcpyAsync(t->off.p, ix.off.data(), sizeof(long long) * ((size_t)nr + 1), hipMemcpyHostToDevice, ctx->stream));
-        CK(hipStreamSynchronize(ctx->stream));
+        int64_t ne64 = 0, ix_dropped = 0;
+        if ((rc = index_build(ctx, first, nr, q.k, q.max_occ, -1, t->codes, t->gpos, t->off, ix_off, &ne64, &ix_dropped))) return rc;
+        const size_t ne = (size_t)ne64;
         t->stats[2]++;
         t->stats[3] += (int64_t)ne;
-        t->stats[4] += ix.dropped_codes;
-        t->stats[7] += (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+        t->stats[4] += ix_dropped;
+        t->stats[7] = ctx->idx_st->stats[6];
         P.n_entries = (int)ne;
         P.search_top = 0;
         for (long long v = 1; v <= (long long)ne; v <<= 1) P.search_top = (int)v;      // the searches' trip counts: fixed here, from the block

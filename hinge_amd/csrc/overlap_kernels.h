@@ -2,7 +2,7 @@
 // front of hinge_trace_local (trace_kernels.h): it says "reads a and b, strand s, about this diagonal" and aligns nothing.
 // Stands where the reference's run script calls DALIGNER on the read DB against itself; not a port of it.
 //
-// Index (host, seed_index.h, one per target BLOCK of consecutive reads): every k-mer of every read of the block at every position,
+// Index (index_kernels.h on the device or seed_index.h on the host; one per target BLOCK of consecutive reads): every k-mer of every read of the block at every position,
 // none across two reads, as (code, gpos) sorted by both; gpos = position in the block's concatenated reads (< 2^31); a code with
 // more than max_occ entries in the block has none.  One block is resident at a time.
 // Job = (query read a, strand, the resident block): Q = read a in the strand's frame (CnsPair::B), alen its length; targets forward.
@@ -30,7 +30,7 @@
 // candidate ranking.  Nothing is read that another wavefront writes; jobs are assigned by blockIdx; no atomics; the only barrier is
 // that of the one-wavefront workgroup, inside wavefront-uniform loops (nh and N are sums of ballots: the same in every lane).
 // Not claimed: chaining; a second stretch of the same pair; k-mers of more than max_occ copies per block; reads of 2^20 or more
-// bases; more than one GPU; parity with DALIGNER's record set; index build speed (host, reported only).
+// bases; more than one GPU; parity with DALIGNER's record set.
 #pragma once
 #include "seed_kernels.h"
 

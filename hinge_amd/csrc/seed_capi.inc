@@ -1,19 +1,17 @@
 // C ABI of `hinge seed` (include/hinge_hip.h, "hinge seed").  Included by hinge_capi.hip.
-// Host work here: the parameters' defaults and ranges, the k-mer index of the draft (seed_index.h; built from the host copy of the
-// draft's bases that hinge_consensus_set_db keeps, uploaded once per call), the jobs (two per read) in batches under the scratch
+// Host work here: the parameters' defaults and ranges, the call of the draft's k-mer index (index_capi.inc: built on the device from
+// the resident bases, or by seed_index.h from the host copy hinge_consensus_set_db keeps), the jobs (two per read) in batches under the scratch
 // budget, the launches, a pick's projection onto its contig (seed_project) and the order of a read's placements.  The kernel:
 // seed_kernels.h.
-#include <chrono>
-
 struct SeedState {
-    DevBuf jobs, out, codes, gpos;
+    DevBuf jobs, out, codes, gpos, off;
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // hinge_seed_last_stats
 };
 
 static void seed_release(hinge_ctx* ctx) {
     SeedState* t = ctx->seed_st;
     if (!t) return;
-    DevBuf* all[] = {&t->jobs, &t->out, &t->codes, &t->gpos};
+    DevBuf* all[] = {&t->jobs, &t->out, &t->codes, &t->gpos, &t->off};
     for (DevBuf* b : all) release(*b);
     delete t;
     ctx->seed_st = nullptr;
@@ -80,22 +78,16 @@ int hinge_seed_run(hinge_ctx* ctx, const hinge_seed_params* params, int64_t n_re
     SeedState* t = ctx->seed_st;
     for (int64_t& v : t->stats) v = 0;
     *n_out = 0;
-    // ---- the index: built from the draft's bases as hinge_consensus_set_db got them, the entries up ---------------------------------------------------------
-    const auto t0 = std::chrono::steady_clock::now();
-    SeedIndex ix;
-    seed_build_index(s->h_bps0.data(), s->h_boff0.data(), s->h_rlen[0].data(), n_contigs, q.k, q.max_occ, ix);
-    const size_t ne = ix.codes.size();
+    // ---- the index (index_capi.inc): on the device from the resident bases, or on the host and up -----------------------------------------------------------
+    std::vector<long long> ix_off;
+    int64_t ne64 = 0, ix_dropped = 0;
     int rc;
-    if ((rc = ensure(ctx, t->codes, sizeof(uint32_t) * std::max<size_t>(ne, 1)))) return rc;
-    if ((rc = ensure(ctx, t->gpos, sizeof(int32_t) * std::max<size_t>(ne, 1)))) return rc;
-    if (ne) {
-        CK(hipMemcpyAsync(t->codes.p, ix.codes.data(), sizeof(uint32_t) * ne, hipMemcpyHostToDevice, ctx->stream));
-        CK(hipMemcpyAsync(t->gpos.p, ix.gpos.data(), sizeof(int32_t) * ne, hipMemcpyHostToDevice, ctx->stream));
-        CK(hipStreamSynchronize(ctx->stream));
-    }
+    index_stats_reset(ctx);
+    if ((rc = index_build(ctx, 0, n_contigs, q.k, q.max_occ, -1, t->codes, t->gpos, t->off, ix_off, &ne64, &ix_dropped))) return rc;
+    const size_t ne = (size_t)ne64;
     t->stats[2] = (int64_t)ne;
-    t->stats[3] = ix.dropped_codes;
-    t->stats[6] = (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+    t->stats[3] = ix_dropped;
+    t->stats[6] = ctx->idx_st->stats[6];
     SeedParams P;
     P.k = q.k; P.window = q.window; P.max_occ = q.max_occ; P.list = q.list; P.n_max = N; P.min_hits = q.min_hits;
     P.n_entries = (int)ne;
@@ -146,7 +138,7 @@ int hinge_seed_run(hinge_ctx* ctx, const hinge_seed_params* params, int64_t n_re
             for (const Cand& c : cand) {
                 if (placed == N) break;
                 int a, ab, ae, bb, be;
-                if (!seed_project(ix.off.data(), n_contigs, q.k, c.gpos, c.p, blen, &a, &ab, &ae, &bb, &be)) continue;
+                if (!seed_project(ix_off.data(), n_contigs, q.k, c.gpos, c.p, blen, &a, &ab, &ae, &bb, &be)) continue;
                 hinge_cns_alignment& o = out[n_total];
                 o.aread = a; o.bread = b; o.comp = c.comp; o.abpos = ab; o.aepos = ae; o.bbpos = bb; o.bepos = be; o.tlen = 0; o.trace_off = 0;
                 count[n_total] = c.cnt;

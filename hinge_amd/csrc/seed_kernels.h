@@ -2,7 +2,7 @@
 // half is hinge_trace_local (trace_kernels.h): it says "read r, strand s, contig c, about this diagonal" and aligns nothing.
 // Stands where demo/ecoli_demo/run.sh:30-37 runs HPC.daligner's seeding; not a port of it.
 //
-// Index (host, seed_index.h): every k-mer of every contig at every position, none across two contigs, as (code, gpos) sorted by
+// Index (index_kernels.h on the device; seed_index.h on the host): every k-mer of every contig at every position, none across two contigs, as (code, gpos) sorted by
 // both; code = 2 bits per base, the first base on top; gpos = position in the concatenated contigs (< 2^31); a code with more than
 // max_occ entries has none.
 // Job = one (read, strand): B = the read in the strand's frame (CnsPair::B), blen its length.

@@ -508,7 +508,7 @@ int hinge_trace_last_stats(hinge_ctx* ctx, int64_t* out);
 /* ---- hinge seed -------------------------------------------------------------------------------------------------------------
  * k-mer placements of reads on the draft: "read r, strand s, contig c, about this diagonal", for hinge_trace_local to align.
  * Not a program of the reference (its run script calls DALIGNER there).  Uses the two DBs of hinge_consensus_set_db.
- *   index      (host, once per call) every k-mer of every contig of DB 0 at every position, none across two contigs, as
+ *   index      (hinge index below; once per call) every k-mer of every contig of DB 0 at every position, none across two contigs, as
  *              (code, gpos) sorted by both; code = 2 bits per base, the first base on top; gpos = position in the concatenated
  *              contigs; a code with more than max_occ entries has none
  *   job        one per (read, strand); B = the read in the strand's frame (comp as in hinge_cns_alignment), blen its length.
@@ -547,15 +547,15 @@ int hinge_seed_run(hinge_ctx* ctx, const hinge_seed_params* params, int64_t n_re
 /* The read count of DB 1 as hinge_consensus_set_db got it: what n_placed and status are sized by when read_ids is NULL. */
 int hinge_seed_db_reads(hinge_ctx* ctx, int64_t* n_reads);
 /* Of the last hinge_seed_run: out[0] jobs, [1] batches, [2] index entries, [3] codes dropped by max_occ, [4] OVERFLOW jobs, [5] reads
- * without placement, [6] microseconds of the index (host build, upload), [7] 0. */
+ * without placement, [6] microseconds of the index (whichever path built it: hinge_index_last_stats), [7] 0. */
 int hinge_seed_last_stats(hinge_ctx* ctx, int64_t* out);
 
 /* ---- hinge overlap -----------------------------------------------------------------------------------------
  * Read-vs-read overlap candidates by k-mer votes: "reads a and b, strand s, about this diagonal", for hinge_trace_local to
  * align.  Not a program of the reference (its run script calls DALIGNER there).  BOTH DBs of hinge_consensus_set_db must be the
  * read DB (so hinge_trace_local is used as it is).
- *   blocks     the reads in blocks of consecutive ids of at most block_bases bases each (a longer read: alone).  Per block (host,
- *              one resident at a time) the index of hinge seed over the block's reads: every k-mer at every position, none
+ *   blocks     the reads in blocks of consecutive ids of at most block_bases bases each (a longer read: alone).  Per block (hinge
+ *              index below; one resident at a time) the index of hinge seed over the block's reads: every k-mer at every position, none
  *              across two reads, as (code, gpos) sorted by both; a code with more than max_occ entries IN THE BLOCK has none
  *   job        one per (read a, strand, block); Q = read a in the strand's frame, alen its length; the targets are forward.
  *              Sampled positions p as in hinge seed.  Every entry of p's code is a hit (b, d, p): b = the read holding gpos,
@@ -590,7 +590,7 @@ int hinge_seed_last_stats(hinge_ctx* ctx, int64_t* out);
  *   cut so that neither happens), cap too small.  HINGE_E_DEVICE: a failed allocation, or an output slot the kernel did not
  *   write (the outputs are poisoned before every launch).  Jobs run in batches under HINGE_OVERLAP_SCRATCH_MB (256).
  * Not claimed: chaining; a second stretch of the same pair; k-mers of more than max_occ copies per block; reads of 2^20 or more
- *   bases; more than one GPU; parity with DALIGNER's record set; index build speed (host, reported only).                       */
+ *   bases; more than one GPU; parity with DALIGNER's record set.                                                                */
 typedef struct hinge_overlap_params {
     int32_t k, step, window, max_occ, list, max_partners, min_hits, pad;
     int64_t block_bases;
@@ -600,13 +600,43 @@ typedef struct hinge_overlap_params {
 int hinge_overlap_run(hinge_ctx* ctx, const hinge_overlap_params* params, int32_t* status, int32_t* hits, int64_t* n_out);
 int hinge_overlap_fetch(hinge_ctx* ctx, int64_t cap, hinge_cns_alignment* out, int32_t* count, int32_t* diag, int32_t* rep);
 /* Of the last hinge_overlap_run: out[0] jobs (read, strand, block), [1] batches, [2] blocks, [3] index entries (all blocks), [4] codes
- * dropped by max_occ, [5] OVERFLOW jobs, [6] TRUNCATED jobs, [7] microseconds of the indexes (host build, upload). */
+ * dropped by max_occ, [5] OVERFLOW jobs, [6] TRUNCATED jobs, [7] microseconds of the indexes (whichever path built them:
+ * hinge_index_last_stats). */
 int hinge_overlap_last_stats(hinge_ctx* ctx, int64_t* out);
+
+/* ---- hinge index -------------------------------------------------------------------------------------------
+ * The k-mer index of sequences [first, first + n_seqs) of DB 0 (hinge_consensus_set_db), as hinge seed and hinge overlap use it.
+ *   entries    one per position x >= k - 1 of every sequence of the range (none across two sequences; a sequence shorter than k
+ *              has none): code = the k bases ending at x, 2 bits per base, the first base on top; gpos = off[c] + x - (k - 1),
+ *              off[c] = the lengths of the range's sequences in front of c (off[n_seqs] = all of them)
+ *   order      by (code, gpos), codes unsigned
+ *   filter     a code with more than max_occ entries has none; dropped_codes counts such codes
+ * On the device (index_kernels.h): the entries are extracted in ascending gpos from the resident bases, sorted by code alone with a
+ * STABLE radix sort (8-bit digits, ceil(2 k / 8) passes: histogram, scan, scatter), flagged by run length, and the kept ones
+ * compacted into the arrays the vote kernels read; only the two counts come back.  Fixed trip counts, nothing read that another
+ * workgroup of the same launch writes, one integer atomic (the count of dropped codes): bit-identical from run to run and value
+ * for value the host build (seed_index.h), which stays as the other path.
+ * where: 1 device, 0 host, -1 HINGE_INDEX_DEVICE (default 1).  A device build needs 16 bytes of scratch per entry plus 4 bytes per
+ * (digit, tile of hinge_index_tile() entries) and the scan's totals; a range that needs more than HINGE_INDEX_SCRATCH_MB (default
+ * 2048; HINGE_INDEX_SCRATCH_BYTES) is built on the host, which is not an error.
+ * k 8..16, max_occ 1..256 (HINGE_E_ARG outside), range outside the DB HINGE_E_RANGE, 2^31 or more bases HINGE_E_CAPACITY before
+ * any launch.  HINGE_E_DEVICE: a failed allocation, or counts that do not fit the entries (kept <= entries and kept + dropped x
+ * (max_occ + 1) <= entries; the scratch is poisoned before the launches).
+ * hinge_index_fetch copies the last hinge_index_build's result: codes / gpos [cap], cap >= *n_entries, off[n_seqs + 1].
+ * Not claimed: an index that persists across calls; several ranges resident at once; more than one GPU.                        */
+int hinge_index_build(hinge_ctx* ctx, int32_t first, int32_t n_seqs, int32_t k, int32_t max_occ, int32_t where, int64_t* n_entries, int64_t* dropped_codes);
+int hinge_index_fetch(hinge_ctx* ctx, int64_t cap, uint32_t* codes, int32_t* gpos, int64_t* off);
+/* Of the last hinge_index_build / hinge_seed_run / hinge_overlap_run, summed over its blocks: [0] entries before the filter, [1] entries kept,
+ * [2] codes dropped, [3] ranges built on the device, [4] ranges built on the host (switch or budget), [5] sort passes of the last
+ * device build, [6] microseconds, [7] scratch bytes in use (the largest range's). */
+int hinge_index_last_stats(hinge_ctx* ctx, int64_t* out);
+/* Entries per tile of the device build's sort (one wavefront's share of a pass). */
+int hinge_index_tile(void);
 
 /* Per-kernel timing with HIP events recorded around every launch on the context's stream.
  * enable(max_launches > 0) starts a fresh recording; report() synchronises and returns total ms and
  * launch count per kernel id in [0, hinge_profile_kernels()).  select() restricts the events to the
- * kernel ids whose bit is set (default: all); two events per launch cost a few microseconds of stream
+ * kernel ids whose bit is set (default: all; ids of 32 and more - the index kernels - get events only while all 32 bits are set); two events per launch cost a few microseconds of stream
  * time each, so a timed region brackets only the kernel it prices.                                 */
 int hinge_profile_enable(hinge_ctx* ctx, int max_launches);
 int hinge_profile_select(hinge_ctx* ctx, uint32_t kernel_mask);

@@ -1,8 +1,10 @@
 #!/usr/bin/env python
 """`hinge overlap` at bench size: the reads of hinge_amd/synth_consensus.py "cns_bench" (4 contigs of ~1.1 Mb at 30x: 18.8 k reads,
 E. coli size) against themselves through hinge_overlap_run, then hinge_trace_local on the candidates.  One JSON line; every figure
-sits in "figures" as {"value": ..., "measured": "gpu" | "host" | "not measured"}:
-  index_ms (host build and upload of every block's index), k_overlap_vote_ms (HIP events, hinge_profile_*), candidates_per_s (by the
+sits in "figures" as {"value": ..., "measured": "gpu" | "host" | "gpu+host" | "not measured"}:
+  index_ms (every block's index; "measured" names the path that built them, from hinge_index_last_stats: the device build of
+  index_kernels.h, or - HINGE_INDEX_DEVICE=0, or a block beyond the scratch budget - the host build and its upload; the index
+  kernels' own time by HIP events is in index_kernels_ms), k_overlap_vote_ms (HIP events, hinge_profile_*), candidates_per_s (by the
   kernel's time), trace_local_ms and its records on the first --align candidates (0 = all), records_written (the executable, with
   --cli), recall: the generator's pairs sharing >= 2 000 contig bases (from the reads' longest records on the contigs they were cut
   from) that are candidates after the mirror step.
@@ -82,10 +84,14 @@ def main():
     for _ in range(args.steps):
         ctx.overlap_run()
         index_us.append(ctx.overlap_stats()["index_us"])
+    ist = ctx.index_last_stats()
+    out["index_stats"] = ist
+    index_path = "gpu" if ist["host_builds"] == 0 else "host" if ist["device_builds"] == 0 else "gpu+host"
     call_ms = (time.time() - t) * 1e3 / args.steps
     prof = ctx.profile_report()
     kernel_ms = prof["k_overlap_vote"][0] / args.steps
-    put("index_ms", round(float(np.mean(index_us)) / 1e3, 3), "host")
+    put("index_ms", round(float(np.mean(index_us)) / 1e3, 3), index_path)
+    put("index_kernels_ms", {k: round(v[0] / args.steps, 3) for k, v in prof.items() if k.startswith("k_index")} if ist["device_builds"] else None, "gpu" if ist["device_builds"] else "not measured")
     put("k_overlap_vote_ms", round(kernel_ms, 3), "gpu")
     put("run_call_ms", round(call_ms, 3), "host")
     put("candidates", int(len(pl)), "gpu")

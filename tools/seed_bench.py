@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """`hinge seed` at bench size: the reads of hinge_amd/synth_consensus.py "cns_bench" (4 contigs of ~1.1 Mb at 30x: 18.8 k reads)
 through hinge_seed_run.  One JSON line:
-  index_ms (bases back from the device, host build, upload), k_seed_vote's time on resident data (HIP events, hinge_profile_*),
+  index_ms with index_path = the path that built it, from hinge_index_last_stats ("gpu": the device build of index_kernels.h, whose
+  kernels' time by HIP events is index_kernels_ms; "host": HINGE_INDEX_DEVICE=0 or a draft beyond the scratch budget - the host build
+  and its upload), k_seed_vote's time on resident data (HIP events, hinge_profile_*),
   reads/s; the share of the generator's records recovered - per read its longest record, of >= 400 contig bases: contig, strand and a
   diagonal within window + 5 % of its length (tests/seed_common.py recall) -; hinge_trace_local's kernel time on the seeded
   placements beside its time on the generator's own; `hinge consensus` on the .las made from the seeded placements, with the bases
@@ -58,6 +60,10 @@ def main():
     rep = ctx.profile_report()
     out["run_call_ms"] = round(call_ms, 3)                                             # index + H2D + kernel + D2H + the host's projection
     out["index_ms"] = round(float(np.mean(index_us)) / 1e3, 3)
+    ist = ctx.index_last_stats()
+    out["index_stats"] = ist
+    out["index_path"] = "gpu" if ist["host_builds"] == 0 else "host" if ist["device_builds"] == 0 else "gpu+host"
+    out["index_kernels_ms"] = {k: round(v[0] / args.steps, 4) for k, v in rep.items() if k.startswith("k_index")} if ist["device_builds"] else None
     out["kernel_ms"] = round(rep["k_seed_vote"][0] / args.steps, 4)
     out["reads_per_s_kernel"] = len(d.reads) / (out["kernel_ms"] * 1e-3) if out["kernel_ms"] else None
     out["reads_per_s_call"] = len(d.reads) / (call_ms * 1e-3)
