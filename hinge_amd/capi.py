@@ -124,6 +124,8 @@ SYMBOLS = [
     ("hinge_seed_last_stats", C.c_int, [_VP, _VP]),
     ("hinge_overlap_run", C.c_int, [_VP, _VP, _VP, _VP, C.POINTER(C.c_int64)]),
     ("hinge_overlap_fetch", C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, _VP]),
+    ("hinge_overlap_run_multi", C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.POINTER(C.c_int64)]),
+    ("hinge_overlap_fetch_round", C.c_int, [_VP, C.c_int64, _VP]),
     ("hinge_overlap_last_stats", C.c_int, [_VP, _VP]),
     ("hinge_index_build", C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("hinge_index_fetch", C.c_int, [_VP, C.c_int64, _VP, _VP, _VP]),
@@ -634,12 +636,17 @@ class Context:
         self._ck(self.lib.hinge_seed_last_stats(self.h, _ptr(st)))
         return dict(zip(("jobs", "batches", "entries", "dropped_codes", "overflow", "unplaced", "index_us"), [int(v) for v in st[:7]]))
 
-    def overlap_run(self, k: int = 0, step: int = 0, window: int = 0, max_occ: int = 0, list_: int = 0, max_partners: int = 0, min_hits: int = 0, block_bases: int = 0):
+    def overlap_run(self, k: int = 0, step: int = 0, window: int = 0, max_occ: int = 0, list_: int = 0, max_partners: int = 0, min_hits: int = 0, block_bases: int = 0,
+                    max_stretches: int = 0, multi: bool = False):
         """hinge_overlap_run (`hinge overlap`): read-vs-read overlap candidates of the reads of Consensus(ctx, read_db, read_db) by
         k-mer votes.  0 = the default (HINGE_OVERLAP_*, else 15, 2, 256, 64, 4096, 64, 6, 16 Mi).  Returns (candidates int64 [m, 7] =
         rows of (aread, bread, comp, abpos, aepos, bbpos, bepos) as trace_local takes them, sorted by (aread, bread, comp), count
         int32 [m], diag int32 [m] = bbpos - abpos, rep int32 [m, 2] = the representative's (d, p), status int32 [n, 2] = per strand 1 NONE,
-        else the bits 2 OVERFLOW and 4 TRUNCATED, hits int32 [n, 2] = hits kept) and leaves the call's figures in overlap_stats()."""
+        else the bits 2 OVERFLOW and 4 TRUNCATED, hits int32 [n, 2] = hits kept) and leaves the call's figures in overlap_stats().
+        max_stretches != 0: hinge_overlap_run_multi with that many rounds (1..8): up to that many candidates per (aread, bread,
+        comp), sorted by round behind the key; the tuple then ends with round int32 [m].  multi=True takes that entry whatever
+        max_stretches is (0 there: HINGE_OVERLAP_MAX_STRETCHES, else 1)."""
+        multi = multi or max_stretches != 0
         nr = C.c_int64(0)
         self._ck(self.lib.hinge_seed_db_reads(self.h, C.byref(nr)))
         n = int(nr.value)
@@ -648,7 +655,10 @@ class Context:
         params[0] = (k, step, window, max_occ, list_, max_partners, min_hits, 0, block_bases)
         m = C.c_int64(0)
         hits = np.zeros((max(n, 1), 2), dtype=np.int32)
-        self._ck(self.lib.hinge_overlap_run(self.h, _ptr(params), _ptr(status), _ptr(hits), C.byref(m)))
+        if multi:
+            self._ck(self.lib.hinge_overlap_run_multi(self.h, _ptr(params), max_stretches, _ptr(status), _ptr(hits), C.byref(m)))
+        else:
+            self._ck(self.lib.hinge_overlap_run(self.h, _ptr(params), _ptr(status), _ptr(hits), C.byref(m)))
         m = m.value
         out = np.zeros(max(m, 1), dtype=CNS_ALN_DTYPE)
         count = np.zeros(max(m, 1), dtype=np.int32)
@@ -656,6 +666,10 @@ class Context:
         rep = np.zeros((max(m, 1), 2), dtype=np.int32)
         self._ck(self.lib.hinge_overlap_fetch(self.h, m, _ptr(out), _ptr(count), _ptr(diag), _ptr(rep)))
         pl = np.stack([out[name][:m].astype(np.int64) for name in ("aread", "bread", "comp", "abpos", "aepos", "bbpos", "bepos")], axis=1) if m else np.zeros((0, 7), np.int64)
+        if multi:
+            rnd = np.zeros(max(m, 1), dtype=np.int32)
+            self._ck(self.lib.hinge_overlap_fetch_round(self.h, m, _ptr(rnd)))
+            return pl, count[:m], diag[:m], rep[:m], status[:n], hits[:n], rnd[:m]
         return pl, count[:m], diag[:m], rep[:m], status[:n], hits[:n]
 
     def overlap_stats(self) -> dict:

@@ -2,12 +2,14 @@
 // Host work here: the parameters' defaults and ranges, the limits of the key packing, the target blocks and the calls of their k-mer
 // indexes (index_capi.inc: built on the device from the resident bases, or by seed_index.h on the host; one block resident at a time), the
 // jobs (two per read) in batches under the scratch budget against every block, a candidate's projection in the record's frame
-// (overlap_project) and the order of the result.  The kernel: overlap_kernels.h.
+// (overlap_project) and the order of the result.  The kernels: overlap_kernels.h (one candidate per (a, b, strand)) and
+// overlap_multi_kernels.h (hinge_overlap_run_multi: up to max_stretches of them); both entry points are overlap_run_impl.
 
-struct OverlapCand { hinge_cns_alignment r; int32_t cnt, diag, d, p; };
+static_assert(OVL_STRETCHES_MAX == HINGE_OVERLAP_MAX_STRETCHES_LIMIT, "the header's limit is the kernel's");
+struct OverlapCand { hinge_cns_alignment r; int32_t cnt, diag, d, p, round; };
 struct OverlapState {
     DevBuf jobs, out, codes, gpos, off;
-    std::vector<OverlapCand> cand;                 // of the last hinge_overlap_run, sorted by (a, b, comp)
+    std::vector<OverlapCand> cand;                 // of the last hinge_overlap_run / _run_multi, sorted by (a, b, comp, round)
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // hinge_overlap_last_stats
 };
 
@@ -20,21 +22,26 @@ static void overlap_release(hinge_ctx* ctx) {
     ctx->ovl_st = nullptr;
 }
 
-// One batch: jobs[0..nj) through k_overlap_vote against the resident block; h_out = ovl_out_ints(max_partners) ints per job.
-static int overlap_batch(hinge_ctx* ctx, const OvlJob* jobs, size_t nj, const OvlParams& P, std::vector<int>& h_out) {
+// One batch: jobs[0..nj) against the resident block; h_out = W ints per job.  S == 0: k_overlap_vote, W = ovl_out_ints(max_partners);
+// S >= 1: k_overlap_vote_multi with S rounds, W = ovl_multi_out_ints(max_partners, S).
+static int overlap_batch(hinge_ctx* ctx, const OvlJob* jobs, size_t nj, const OvlParams& P, int S, std::vector<int>& h_out) {
     OverlapState* t = ctx->ovl_st;
     CnsState* s = ctx->cns;
-    const size_t out_ints = nj * (size_t)ovl_out_ints(P.max_partners);
+    const size_t out_ints = nj * (size_t)(S ? ovl_multi_out_ints(P.max_partners, S) : ovl_out_ints(P.max_partners));
     int rc;
     if ((rc = ensure(ctx, t->jobs, sizeof(OvlJob) * nj))) return rc;
     if ((rc = ensure(ctx, t->out, sizeof(int) * out_ints))) return rc;
     CK(hipMemcpyAsync(t->jobs.p, jobs, sizeof(OvlJob) * nj, hipMemcpyHostToDevice, ctx->stream));
     CK(hipMemsetAsync(t->out.p, 0xff, sizeof(int) * out_ints, ctx->stream));   // poison: a slot the kernel did not write is seen as such
     CnsSeqs SB{(const unsigned char*)s->bps[0].p, (const long long*)s->boff[0].p, (const int*)s->rlen[0].p};
-    {
+    if (S == 0) {
         ProfScope _ps(ctx, KID_OVERLAP_VOTE);
         hipLaunchKernelGGL(k_overlap_vote, dim3((unsigned)nj), dim3(64), ovl_lds_bytes(P.list), ctx->stream, SB, (const OvlJob*)t->jobs.p, (int)nj, P, (const unsigned*)t->codes.p,
                            (const int*)t->gpos.p, (const long long*)t->off.p, (int*)t->out.p);
+    } else {
+        ProfScope _ps(ctx, KID_OVERLAP_VOTE_MULTI);
+        hipLaunchKernelGGL(k_overlap_vote_multi, dim3((unsigned)nj), dim3(64), ovl_multi_lds_bytes(P.list), ctx->stream, SB, (const OvlJob*)t->jobs.p, (int)nj, P, S,
+                           (const unsigned*)t->codes.p, (const int*)t->gpos.p, (const long long*)t->off.p, (int*)t->out.p);
     }
     CK(hipGetLastError());
     h_out.resize(out_ints);
@@ -43,11 +50,10 @@ static int overlap_batch(hinge_ctx* ctx, const OvlJob* jobs, size_t nj, const Ov
     return HINGE_OK;
 }
 
-extern "C" {
-
-int hinge_overlap_run(hinge_ctx* ctx, const hinge_overlap_params* params, int32_t* status, int32_t* hits, int64_t* n_out) {
+// hinge_overlap_run (S == 0: k_overlap_vote, one round) and hinge_overlap_run_multi (S = 1 .. 8 rounds of k_overlap_vote_multi).
+static int overlap_run_impl(hinge_ctx* ctx, const hinge_overlap_params* params, int S, int32_t* status, int32_t* hits, int64_t* n_out) {
     if (!ctx || !ctx->cns || !n_out || (ctx->cns->n_seq[0] > 0 && !status))
-        return fail(ctx, HINGE_E_ARG, "hinge_overlap_run: bad arguments (call hinge_consensus_set_db with the read DB for both DBs first)");
+        return fail(ctx, HINGE_E_ARG, "hinge_overlap_run / _run_multi: bad arguments (call hinge_consensus_set_db with the read DB for both DBs first)");
     hinge_overlap_params q = params ? *params : hinge_overlap_params{0, 0, 0, 0, 0, 0, 0, 0};
     if (q.k == 0) q.k = (int32_t)seed_env("HINGE_OVERLAP_K", 15);
     if (q.step == 0) q.step = (int32_t)seed_env("HINGE_OVERLAP_STEP", 2);
@@ -61,10 +67,10 @@ int hinge_overlap_run(hinge_ctx* ctx, const hinge_overlap_params* params, int32_
     if (q.k < SEED_K_MIN || q.k > SEED_K_MAX || q.step < 1 || q.step > 65536 || !pow2(q.window) || q.window < SEED_WINDOW_MIN || q.window > SEED_WINDOW_MAX || q.max_occ < 1 ||
         q.max_occ > SEED_OCC_MAX || !pow2(q.list) || q.list < OVL_LIST_MIN || q.list > OVL_LIST_MAX || q.max_partners < 1 || q.max_partners > OVL_PARTNERS_MAX || q.min_hits < 1 ||
         q.block_bases < 1 || q.block_bases >= (1ll << 31))
-        return fail(ctx, HINGE_E_ARG, "hinge_overlap_run: k 8..16, step 1..65536, window a power of two 16..65536, max_occ 1..256, list a power of two 64..8192, max_partners 1..4096, min_hits >= 1, block_bases 1..2^31-1 (0 = the default)");
+        return fail(ctx, HINGE_E_ARG, "hinge_overlap_run / _run_multi: k 8..16, step 1..65536, window a power of two 16..65536, max_occ 1..256, list a power of two 64..8192, max_partners 1..4096, min_hits >= 1, block_bases 1..2^31-1 (0 = the default)");
     CnsState* s = ctx->cns;
     const int n = s->n_seq[0];
-    if (s->n_seq[1] != n || s->h_rlen[1] != s->h_rlen[0]) return fail(ctx, HINGE_E_ARG, "hinge_overlap_run: both DBs of hinge_consensus_set_db must be the read DB");
+    if (s->n_seq[1] != n || s->h_rlen[1] != s->h_rlen[0]) return fail(ctx, HINGE_E_ARG, "hinge_overlap_run / _run_multi: both DBs of hinge_consensus_set_db must be the read DB");
     // ---- the limits of the key packing, before any launch; the blocks: consecutive reads of at most block_bases bases (a longer read: alone) -------------------
     std::vector<int> bfirst;                        // [n_blocks + 1]
     {
@@ -72,10 +78,10 @@ int hinge_overlap_run(hinge_ctx* ctx, const hinge_overlap_params* params, int32_
         int reads = 0;
         for (int r = 0; r < n; r++) {
             const int len = s->h_rlen[0][(size_t)r];
-            if (len > OVL_READ_MAX) return fail(ctx, HINGE_E_CAPACITY, "hinge_overlap_run: a read of 2^20 or more bases (the hit key holds a position in 20 bits)");
+            if (len > OVL_READ_MAX) return fail(ctx, HINGE_E_CAPACITY, "hinge_overlap_run / _run_multi: a read of 2^20 or more bases (the hit key holds a position in 20 bits)");
             if (r == 0 || bases + len > q.block_bases || reads == OVL_BLOCK_READS_MAX) { bfirst.push_back(r); bases = 0; reads = 0; }
             bases += len; reads++;
-            if (bases >= (1ll << 31)) return fail(ctx, HINGE_E_CAPACITY, "hinge_overlap_run: a block of 2^31 or more bases");
+            if (bases >= (1ll << 31)) return fail(ctx, HINGE_E_CAPACITY, "hinge_overlap_run / _run_multi: a block of 2^31 or more bases");
         }
         bfirst.push_back(n);
     }
@@ -89,7 +95,9 @@ int hinge_overlap_run(hinge_ctx* ctx, const hinge_overlap_params* params, int32_
     for (int r = 0; r < 2 * n; r++) { status[r] = OVL_ST_NONE; if (hits) hits[r] = 0; }
     if (n == 0) return HINGE_OK;
     const size_t lds = ovl_lds_bytes(q.list);
-    if (lds > 48 * 1024) CK(hipFuncSetAttribute((const void*)k_overlap_vote, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (S == 0 && lds > 48 * 1024) CK(hipFuncSetAttribute((const void*)k_overlap_vote, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (S > 0 && ovl_multi_lds_bytes(q.list) > 48 * 1024)
+        CK(hipFuncSetAttribute((const void*)k_overlap_vote_multi, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ovl_multi_lds_bytes(q.list)));
     OvlParams P;
     P.k = q.k; P.window = q.window; P.max_occ = q.max_occ; P.list = q.list; P.max_partners = q.max_partners; P.min_hits = q.min_hits;
     // ---- the jobs: two per read, the same for every block ------------------------------------------------------------------------------------
@@ -100,7 +108,8 @@ int hinge_overlap_run(hinge_ctx* ctx, const hinge_overlap_params* params, int32_
     }
     long long budget = std::max(1ll, seed_env("HINGE_OVERLAP_SCRATCH_MB", 256)) << 20;
     budget = std::max(1ll, seed_env("HINGE_OVERLAP_SCRATCH_BYTES", budget));
-    const int W = ovl_out_ints(q.max_partners);
+    const int W = S ? ovl_multi_out_ints(q.max_partners, S) : ovl_out_ints(q.max_partners);       // (a job of S rounds is S times as wide: batches shrink)
+    const int rounds = std::max(S, 1), head = OVL_HEAD + S;
     const long long per_job = (long long)sizeof(OvlJob) + (long long)sizeof(int) * W;
     const int64_t per_batch = std::min<long long>(std::max<long long>(budget / per_job, 1), 1 << 20);
     std::vector<int> h_out;
@@ -126,30 +135,38 @@ int hinge_overlap_run(hinge_ctx* ctx, const hinge_overlap_params* params, int32_
         // ---- every job against it, in batches under the scratch budget -------------------------------------------------------------------------------
         for (int64_t j0 = 0; j0 < 2 * (int64_t)n; j0 += per_batch) {
             const int64_t j1 = std::min<int64_t>(2 * (int64_t)n, j0 + per_batch);
-            if ((rc = overlap_batch(ctx, jobs.data() + j0, (size_t)(j1 - j0), P, h_out))) return rc;
+            if ((rc = overlap_batch(ctx, jobs.data() + j0, (size_t)(j1 - j0), P, S, h_out))) return rc;
             t->stats[0] += j1 - j0;
             t->stats[1]++;
             for (int64_t j = j0; j < j1; j++) {
                 const int* o = h_out.data() + (size_t)(j - j0) * (size_t)W;
                 const OvlJob& J = jobs[(size_t)j];
                 const bool st_ok = o[0] == OVL_ST_OK || o[0] == OVL_ST_NONE || o[0] == OVL_ST_OVERFLOW || o[0] == OVL_ST_TRUNCATED || o[0] == (OVL_ST_OVERFLOW | OVL_ST_TRUNCATED);
-                if (!st_ok || o[1] < 0 || o[1] > q.max_partners || o[2] < 0 || o[2] > q.list || (o[1] > 0 && (o[2] < 1 || o[0] == OVL_ST_NONE)) || o[3] != 0)
-                    return fail(ctx, HINGE_E_DEVICE, "hinge_overlap_run: a job's status slot was never written");
+                int round_sum = S ? 0 : o[1];                               // the head of S rounds: the number written in each
+                bool rounds_ok = true;
+                for (int r = 0; r < S; r++) {
+                    if (o[OVL_HEAD + r] < 0 || o[OVL_HEAD + r] > q.max_partners || (r > 0 && o[OVL_HEAD + r] > 0 && o[OVL_HEAD + r - 1] == 0)) rounds_ok = false;
+                    round_sum += o[OVL_HEAD + r];
+                }
+                if (!st_ok || !rounds_ok || round_sum != o[1] || o[1] < 0 || o[1] > rounds * q.max_partners || o[2] < 0 || o[2] > q.list || (o[1] > 0 && (o[2] < 1 || o[0] == OVL_ST_NONE)) || o[3] != 0)
+                    return fail(ctx, HINGE_E_DEVICE, "hinge_overlap_run / _run_multi: a job's status slot was never written");
                 if (hits) hits[j] += o[2];
                 if (o[0] != OVL_ST_NONE) status[j] = (status[j] == OVL_ST_NONE ? 0 : status[j]) | o[0];
                 if (o[0] != OVL_ST_NONE && (o[0] & OVL_ST_OVERFLOW)) t->stats[5]++;
                 if (o[0] != OVL_ST_NONE && (o[0] & OVL_ST_TRUNCATED)) t->stats[6]++;
-                for (int c = 0; c < o[1]; c++) {
-                    const int* pk = o + OVL_HEAD + 4 * c;
+                for (int x = 0, r = 0, c0 = 0; x < o[1]; x++) {                    // the x-th candidate: slot c of section r
+                    while (S && x - c0 == o[OVL_HEAD + r]) { c0 = x; r++; }   // (the sections' counts sum to o[1]: checked above)
+                    const int c = x - c0;
+                    const int* pk = o + head + 4 * (r * q.max_partners + c);
                     const int b = pk[0];
                     const bool b_ok = b >= first && b < first + nr && b != J.a;
                     const int blen = b_ok ? s->h_rlen[0][(size_t)b] : 0;
                     OverlapCand oc;
                     if (!b_ok || pk[1] < q.min_hits || pk[1] > o[2] || pk[2] < 1 || pk[2] >= J.alen + blen || pk[3] < 0 || pk[3] > J.alen - q.k ||
                         !overlap_project(J.alen, blen, J.comp, pk[2], q.k, &oc.r.abpos, &oc.r.aepos, &oc.r.bbpos, &oc.r.bepos, &oc.diag))
-                        return fail(ctx, HINGE_E_DEVICE, "hinge_overlap_run: a candidate's slot was never written");
+                        return fail(ctx, HINGE_E_DEVICE, "hinge_overlap_run / _run_multi: a candidate's slot was never written");
                     oc.r.aread = J.a; oc.r.bread = b; oc.r.comp = J.comp; oc.r.tlen = 0; oc.r.trace_off = 0;
-                    oc.cnt = pk[1]; oc.d = pk[2]; oc.p = pk[3];
+                    oc.cnt = pk[1]; oc.d = pk[2]; oc.p = pk[3]; oc.round = r;
                     t->cand.push_back(oc);
                 }
             }
@@ -158,9 +175,30 @@ int hinge_overlap_run(hinge_ctx* ctx, const hinge_overlap_params* params, int32_
     std::sort(t->cand.begin(), t->cand.end(), [](const OverlapCand& u, const OverlapCand& v) {
         if (u.r.aread != v.r.aread) return u.r.aread < v.r.aread;
         if (u.r.bread != v.r.bread) return u.r.bread < v.r.bread;
-        return u.r.comp < v.r.comp;
+        if (u.r.comp != v.r.comp) return u.r.comp < v.r.comp;
+        return u.round < v.round;
     });
     *n_out = (int64_t)t->cand.size();
+    return HINGE_OK;
+}
+
+extern "C" {
+
+int hinge_overlap_run(hinge_ctx* ctx, const hinge_overlap_params* params, int32_t* status, int32_t* hits, int64_t* n_out) {
+    return overlap_run_impl(ctx, params, 0, status, hits, n_out);
+}
+
+int hinge_overlap_run_multi(hinge_ctx* ctx, const hinge_overlap_params* params, int32_t max_stretches, int32_t* status, int32_t* hits, int64_t* n_out) {
+    if (max_stretches == 0) max_stretches = (int32_t)seed_env("HINGE_OVERLAP_MAX_STRETCHES", 1);
+    if (max_stretches < 1 || max_stretches > OVL_STRETCHES_MAX) return fail(ctx, HINGE_E_ARG, "hinge_overlap_run_multi: max_stretches 1..8 (0 = HINGE_OVERLAP_MAX_STRETCHES, else 1)");
+    return overlap_run_impl(ctx, params, max_stretches, status, hits, n_out);
+}
+
+int hinge_overlap_fetch_round(hinge_ctx* ctx, int64_t cap, int32_t* round) {
+    if (!ctx || !ctx->ovl_st || cap < 0 || (cap > 0 && !round)) return fail(ctx, HINGE_E_ARG, "hinge_overlap_fetch_round: no hinge_overlap_run yet, or bad arguments");
+    const std::vector<OverlapCand>& c = ctx->ovl_st->cand;
+    if ((int64_t)c.size() > cap) return fail(ctx, HINGE_E_CAPACITY, "hinge_overlap_fetch_round: the output array must hold what the run counted");
+    for (size_t x = 0; x < c.size(); x++) round[x] = c[x].round;
     return HINGE_OK;
 }
 

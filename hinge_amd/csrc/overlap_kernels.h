@@ -29,7 +29,7 @@
 // per-group reduction: element i takes the better of itself and element i + s while both have the same b), N / 64 chunks of the
 // candidate ranking.  Nothing is read that another wavefront writes; jobs are assigned by blockIdx; no atomics; the only barrier is
 // that of the one-wavefront workgroup, inside wavefront-uniform loops (nh and N are sums of ballots: the same in every lane).
-// Not claimed: chaining; a second stretch of the same pair; k-mers of more than max_occ copies per block; reads of 2^20 or more
+// Not claimed: chaining; a second stretch of the same pair (k_overlap_vote_multi, overlap_multi_kernels.h, finds those); k-mers of more than max_occ copies per block; reads of 2^20 or more
 // bases; more than one GPU; parity with DALIGNER's record set.
 #pragma once
 #include "seed_kernels.h"

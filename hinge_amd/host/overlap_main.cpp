@@ -1,5 +1,5 @@
 // overlap  ==  `hinge overlap READ_DB OUT.las [--k K] [--step S] [--window W] [--max-occ C] [--list L] [--max-partners N] [--min-hits H] [--block-bases B]
-//                              [--min-len M] [--max-err E] [--tspace T] [--band W] [--band-max W]`
+//                              [--max-stretches S] [--min-len M] [--max-err E] [--tspace T] [--band W] [--band-max W]`
 // Not a program of the reference: it stands where the reference's run script calls DALIGNER (HPC.daligner + LAsort / LAmerge) on the
 // read DB against itself to get the read-vs-read .las that `hinge filter` opens.  The candidates - "reads a and b, strand, about this
 // diagonal" - are found by k-mer votes behind the C ABI (hinge_overlap_run, include/hinge_hip.h) and aligned by hinge_trace_local,
@@ -11,6 +11,25 @@
 //   filter      a record stays with both aligned lengths >= M (1000) and diffs / (aepos - abpos) <= E (0.30)
 //   pairs       a pair is written only if both of its directed records stay
 //   output      LAsort order (aread, bread, comp, abpos); trace values one byte up to tspace 125, as paf2las writes them
+// --max-stretches S (1..8; default HINGE_OVERLAP_MAX_STRETCHES, else 1; 1 is the path above, call for call): up to S records per
+// (aread, bread, comp), one per stretch - a repeat inside both reads, a circular genome's wrap
+//   candidates  hinge_overlap_run_multi: up to S per (a, b, comp), by rounds of pick and suppress
+//   canonical   a candidate (a, b, comp, diag) with a > b becomes (b, a, comp, mirrored diag)
+//   merge       per (a < b, comp) the diagonals of both directions sorted; neighbours closer than `window` merge (single linkage);
+//               a cluster's representative is its member found from a's side of the largest count - where a's side found it, the
+//               diagonal that goes into the alignment is the one the path above would take, so a set without a second stretch gives
+//               the same bytes -, without one its member of the largest count; ties to the smaller diagonal
+//   alignment   every cluster projected as above - both reads whole along the representative's diagonal - through
+//               hinge_trace_local; --min-len and --max-err as above
+//   duplicates  the records of a key in the order (A length descending, abpos, bbpos): one is dropped if against a record already
+//               kept their A ranges intersect by more than half the shorter one AND the smaller of |difference of the begin
+//               diagonals bbpos - abpos| and |difference of the end diagonals bepos - aepos| is below `window` - the same alignment
+//               reached from two bands, or a cut piece of it; a repeat's cross alignment lies a copy distance away on both ends
+//   mirror      every kept record's mirror is the same stretch from read b through hinge_trace_run, tied to its origin by index;
+//               a stretch is written only with both records
+//   output      (aread, bread, comp, abpos, bbpos)
+// Not claimed: two stretches on one diagonal; a weaker stretch inside the band that a stronger one's alignment settles in (after a
+// TOUCHED widening both boxes may return the same optimum: the duplicate rule then leaves one); stretches of fewer than min-hits hits.
 #include "host_common.h"
 
 #include <unordered_set>
@@ -19,8 +38,9 @@ using namespace hh;
 
 static void usage() {
     fprintf(stderr, "usage: overlap <read db> <out.las> [--k K] [--step S] [--window W] [--max-occ C] [--list L] [--max-partners N] [--min-hits H] [--block-bases B]\n"
-                    "               [--min-len M] [--max-err E] [--tspace T] [--band W] [--band-max W]\n"
-                    "       read-vs-read overlaps of <read db> by k-mer votes and banded local alignment, as the .las `hinge filter` reads\n");
+                    "               [--max-stretches S] [--min-len M] [--max-err E] [--tspace T] [--band W] [--band-max W]\n"
+                    "       read-vs-read overlaps of <read db> by k-mer votes and banded local alignment, as the .las `hinge filter` reads\n"
+                    "       --max-stretches S: up to S (1..8) records per (aread, bread, strand), one per stretch; default HINGE_OVERLAP_MAX_STRETCHES, else 1\n");
 }
 
 // both reads whole along the record-frame diagonal (bbpos - abpos), clamped to both; the rule of overlap_project (overlap_kernels.h)
@@ -39,6 +59,7 @@ int main(int argc, char* argv[]) {
     memset(&prm, 0, sizeof(prm));                   // the library's defaults (15, 2, 256, 64, 4096, 64, 6, 16 Mi)
     int min_len = 1000, tspace = 100, band = 0, band_max = 0;
     double max_err = 0.30;
+    int stretches = 0;                              // 0: not given
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto text = [&](const char* name) -> const char* {
@@ -58,6 +79,10 @@ int main(int argc, char* argv[]) {
         else if (a == "--max-partners") prm.max_partners = (int32_t)val("--max-partners");
         else if (a == "--min-hits") prm.min_hits = (int32_t)val("--min-hits");
         else if (a == "--block-bases") prm.block_bases = (int64_t)val("--block-bases");
+        else if (a == "--max-stretches") {
+            stretches = (int)val("--max-stretches");
+            if (stretches > HINGE_OVERLAP_MAX_STRETCHES_LIMIT) { fprintf(stderr, "overlap: --max-stretches needs a number in 1..8\n"); usage(); return 1; }
+        }
         else if (a == "--min-len") min_len = (int)val("--min-len");
         else if (a == "--tspace") tspace = (int)val("--tspace");
         else if (a == "--band") band = (int)val("--band");
@@ -72,6 +97,12 @@ int main(int argc, char* argv[]) {
         else pos.push_back(a);
     }
     if (pos.size() != 2 || tspace > 32767) { usage(); return 1; }
+    if (stretches == 0) {
+        const char* g = getenv("HINGE_OVERLAP_MAX_STRETCHES");
+        stretches = (g && *g) ? atoi(g) : 1;
+        if (stretches < 1 || stretches > HINGE_OVERLAP_MAX_STRETCHES_LIMIT) { fprintf(stderr, "overlap: HINGE_OVERLAP_MAX_STRETCHES needs a number in 1..8\n"); usage(); return 1; }
+    }
+    const bool multi = stretches > 1;
     PhaseTimer tm("overlap");
     CtxInit gpu;
     gpu.start();
@@ -92,17 +123,56 @@ int main(int argc, char* argv[]) {
     // ---- the candidates, made symmetric ------------------------------------------------------------------------------------------
     std::vector<int32_t> jstatus((size_t)std::max(2 * n_reads, 2));
     int64_t n_cand = 0;
-    if (hinge_overlap_run(ctx, &prm, jstatus.data(), nullptr, &n_cand) != HINGE_OK) die("votes");
+    if ((multi ? hinge_overlap_run_multi(ctx, &prm, stretches, jstatus.data(), nullptr, &n_cand) : hinge_overlap_run(ctx, &prm, jstatus.data(), nullptr, &n_cand)) != HINGE_OK) die("votes");
     std::vector<hinge_cns_alignment> cand((size_t)std::max<int64_t>(n_cand, 1));
     std::vector<int32_t> count((size_t)std::max<int64_t>(n_cand, 1)), diag((size_t)std::max<int64_t>(n_cand, 1));
     if (hinge_overlap_fetch(ctx, n_cand, cand.data(), count.data(), diag.data(), nullptr) != HINGE_OK) die("votes");
     cand.resize((size_t)n_cand);
+    std::vector<int64_t> per_round((size_t)stretches, 0);
+    if (multi) {
+        std::vector<int32_t> round((size_t)std::max<int64_t>(n_cand, 1));
+        if (hinge_overlap_fetch_round(ctx, n_cand, round.data()) != HINGE_OK) die("votes");
+        for (int64_t x = 0; x < n_cand; x++) per_round[(size_t)round[(size_t)x]]++;
+    }
     int64_t ost[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     (void)hinge_overlap_last_stats(ctx, ost);
     tm.mark("index + votes");
     const int k = prm.k ? prm.k : (getenv("HINGE_OVERLAP_K") && *getenv("HINGE_OVERLAP_K") ? atoi(getenv("HINGE_OVERLAP_K")) : 15);
-    int64_t mirrored = 0;
-    {
+    const int window = prm.window ? prm.window : (getenv("HINGE_OVERLAP_WINDOW") && *getenv("HINGE_OVERLAP_WINDOW") ? atoi(getenv("HINGE_OVERLAP_WINDOW")) : 256);
+    int64_t mirrored = 0, merged = 0;
+    if (multi) {
+        // ---- the canonical frame and the merge: per (a < b, comp) the diagonals of both directions, clustered by single linkage -----
+        struct Canon { int a, b, comp; long long diag; int cnt, from_a; };
+        std::vector<Canon> cn;
+        cn.reserve((size_t)n_cand);
+        for (int64_t x = 0; x < n_cand; x++) {
+            const hinge_cns_alignment& r = cand[(size_t)x];
+            const int alen = db.rlen[(size_t)r.aread], blen = db.rlen[(size_t)r.bread];
+            if (r.aread < r.bread) cn.push_back(Canon{r.aread, r.bread, r.comp, diag[(size_t)x], count[(size_t)x], 1});
+            else cn.push_back(Canon{r.bread, r.aread, r.comp, r.comp ? (long long)alen - blen + diag[(size_t)x] : -(long long)diag[(size_t)x], count[(size_t)x], 0});
+        }
+        std::sort(cn.begin(), cn.end(), [](const Canon& x, const Canon& y) {
+            if (x.a != y.a) return x.a < y.a;
+            if (x.b != y.b) return x.b < y.b;
+            if (x.comp != y.comp) return x.comp < y.comp;
+            if (x.diag != y.diag) return x.diag < y.diag;
+            return x.from_a > y.from_a;
+        });
+        cand.clear();
+        for (size_t x0 = 0; x0 < cn.size();) {
+            size_t x1 = x0 + 1, best = x0;
+            while (x1 < cn.size() && cn[x1].a == cn[x0].a && cn[x1].b == cn[x0].b && cn[x1].comp == cn[x0].comp && cn[x1].diag - cn[x1 - 1].diag < window) {
+                const Canon &c = cn[x1], &q = cn[best];            // a's side first; then the largest count; then the smaller diagonal (the earlier one)
+                if (c.from_a > q.from_a || (c.from_a == q.from_a && c.cnt > q.cnt)) best = x1;
+                x1++;
+            }
+            merged += (int64_t)(x1 - x0) - 1;
+            hinge_cns_alignment m;
+            m.aread = cn[best].a; m.bread = cn[best].b; m.comp = cn[best].comp; m.tlen = 0; m.trace_off = 0;
+            if (along(db.rlen[(size_t)m.aread], db.rlen[(size_t)m.bread], cn[best].diag, k, m)) cand.push_back(m);
+            x0 = x1;
+        }
+    } else {
         std::unordered_set<uint64_t> have;
         have.reserve((size_t)n_cand * 2 + 16);
         for (const hinge_cns_alignment& r : cand) have.insert(pair_key(r.aread, r.bread, r.comp));
@@ -136,7 +206,7 @@ int main(int argc, char* argv[]) {
         if (g && *g) room = std::max(atoi(g), 0);
     }
     const int64_t chunk_records = 1 << 18;
-    struct Kept { hinge_cns_alignment r; int32_t diffs; int64_t toff; };
+    struct Kept { hinge_cns_alignment r; int32_t diffs; int64_t toff; int64_t origin; };   // origin: the element of the round's input
     std::vector<Kept> kept;
     std::vector<uint16_t> ktrace;
     int64_t aligned = 0, asym = 0;
@@ -168,7 +238,7 @@ int main(int argc, char* argv[]) {
                 if (status[(size_t)(2 * x)] != 0) { dropped++; continue; }
                 aligned++;
                 if (r.aepos - r.abpos < min_len || r.bepos - r.bbpos < min_len || (double)diffs[(size_t)x] > max_err * (double)(r.aepos - r.abpos)) { dropped++; continue; }
-                kept.push_back(Kept{r, diffs[(size_t)x], (int64_t)ktrace.size()});
+                kept.push_back(Kept{r, diffs[(size_t)x], (int64_t)ktrace.size(), x0 + x});
                 ktrace.insert(ktrace.end(), trace.begin() + r.trace_off, trace.begin() + r.trace_off + r.tlen);
             }
             x0 = x1;
@@ -177,8 +247,35 @@ int main(int argc, char* argv[]) {
     std::vector<hinge_cns_alignment> first;
     for (const hinge_cns_alignment& r : cand)
         if (r.aread < r.bread) first.push_back(r);
-    int64_t unaligned = 0;
+    int64_t unaligned = 0, duplicates = 0;
     align_round(first, true, unaligned);
+    if (multi) {
+        // ---- duplicates: per key in the order (A length descending, abpos, bbpos), against the records already kept ------------------
+        std::sort(kept.begin(), kept.end(), [&](const Kept& x, const Kept& y) {
+            if (by_key(x.r, y.r) || by_key(y.r, x.r)) return by_key(x.r, y.r);
+            const int lx = x.r.aepos - x.r.abpos, ly = y.r.aepos - y.r.abpos;
+            if (lx != ly) return lx > ly;
+            if (x.r.abpos != y.r.abpos) return x.r.abpos < y.r.abpos;
+            if (x.r.bbpos != y.r.bbpos) return x.r.bbpos < y.r.bbpos;
+            return x.origin < y.origin;
+        });
+        std::vector<Kept> uniq;
+        size_t key0 = 0;                            // where the current key's kept records begin in uniq
+        for (const Kept& q : kept) {
+            if (!uniq.empty() && (by_key(uniq.back().r, q.r) || by_key(q.r, uniq.back().r))) key0 = uniq.size();
+            bool dup = false;
+            for (size_t u = key0; u < uniq.size() && !dup; u++) {
+                const hinge_cns_alignment &r = q.r, &o = uniq[u].r;
+                const long long inter = (long long)std::min(r.aepos, o.aepos) - std::max(r.abpos, o.abpos);
+                const long long near = std::min(std::llabs(((long long)r.bbpos - r.abpos) - ((long long)o.bbpos - o.abpos)), std::llabs(((long long)r.bepos - r.aepos) - ((long long)o.bepos - o.aepos)));
+                dup = 2 * inter > std::min(r.aepos - r.abpos, o.aepos - o.abpos) && near < window;
+            }
+            if (dup) duplicates++;
+            else uniq.push_back(q);
+        }
+        kept.swap(uniq);
+    }
+    const size_t n_first = kept.size();
     std::vector<hinge_cns_alignment> second;
     second.reserve(kept.size());
     for (const Kept& q : kept) {
@@ -190,17 +287,42 @@ int main(int argc, char* argv[]) {
         else { m.abpos = blen - r.bepos; m.aepos = blen - r.bbpos; m.bbpos = alen - r.aepos; m.bepos = alen - r.abpos; }
         second.push_back(m);
     }
-    std::sort(second.begin(), second.end(), by_key);
-    align_round(second, false, asym);
-    std::sort(kept.begin(), kept.end(), [&](const Kept& x, const Kept& y) { return by_key(x.r, y.r); });
+    std::vector<size_t> order;                      // the elements of kept that are written, in the file's order
+    if (multi) {
+        // ---- the mirrors, tied to their origins by index: second[v] is the mirror of kept[perm[v]]; a stretch is written with both ------
+        std::vector<size_t> perm(second.size());
+        for (size_t v = 0; v < perm.size(); v++) perm[v] = v;
+        std::sort(perm.begin(), perm.end(), [&](size_t x, size_t y) { return by_key(second[x], second[y]) || (!by_key(second[y], second[x]) && x < y); });
+        std::vector<hinge_cns_alignment> sorted_second(second.size());
+        for (size_t v = 0; v < perm.size(); v++) sorted_second[v] = second[perm[v]];
+        align_round(sorted_second, false, asym);
+        for (size_t v = n_first; v < kept.size(); v++) {
+            order.push_back(perm[(size_t)kept[v].origin]);
+            order.push_back(v);
+        }
+        std::sort(order.begin(), order.end(), [&](size_t x, size_t y) {
+            const hinge_cns_alignment &u = kept[x].r, &w = kept[y].r;
+            if (by_key(u, w) || by_key(w, u)) return by_key(u, w);
+            if (u.abpos != w.abpos) return u.abpos < w.abpos;
+            if (u.bbpos != w.bbpos) return u.bbpos < w.bbpos;
+            return x < y;
+        });
+    } else {
+        std::sort(second.begin(), second.end(), by_key);
+        align_round(second, false, asym);
+        std::sort(kept.begin(), kept.end(), [&](const Kept& x, const Kept& y) { return by_key(x.r, y.r); });
+    }
     tm.mark("align + trace");
 
     // ---- a pair only with both of its directed records; the .las in LAsort order (aread, bread, comp, abpos: one record per key) ---------
-    std::unordered_set<uint64_t> stay;
-    stay.reserve(kept.size() * 2 + 16);
-    for (const Kept& q : kept) stay.insert(pair_key(q.r.aread, q.r.bread, q.r.comp));
-    int64_t written = 0;
-    for (const Kept& q : kept) written += stay.count(pair_key(q.r.bread, q.r.aread, q.r.comp)) ? 1 : 0;
+    if (!multi) {
+        std::unordered_set<uint64_t> stay;
+        stay.reserve(kept.size() * 2 + 16);
+        for (const Kept& q : kept) stay.insert(pair_key(q.r.aread, q.r.bread, q.r.comp));
+        for (size_t x = 0; x < kept.size(); x++)
+            if (stay.count(pair_key(kept[x].r.bread, kept[x].r.aread, kept[x].r.comp))) order.push_back(x);
+    }
+    const int64_t written = (int64_t)order.size();
     FILE* fo = fopen(pos[1].c_str(), "wb");
     if (!fo) { fprintf(stderr, "overlap: cannot write %s\n", pos[1].c_str()); quit(1); }
     const int32_t ts32 = tspace;
@@ -209,8 +331,8 @@ int main(int argc, char* argv[]) {
     const int tbytes = tspace <= 125 ? 1 : 2;
     std::vector<uint8_t> tb;
     std::vector<char> has_record((size_t)std::max(n_reads, 1), 0);
-    for (const Kept& q : kept) {
-        if (!stay.count(pair_key(q.r.bread, q.r.aread, q.r.comp))) continue;
+    for (const size_t at : order) {
+        const Kept& q = kept[at];
         const hinge_cns_alignment& r = q.r;
         has_record[(size_t)r.aread] = 1;
         uint8_t rec[40];
@@ -229,6 +351,12 @@ int main(int argc, char* argv[]) {
     if (fclose(fo) != 0) { fprintf(stderr, "overlap: cannot write %s\n", pos[1].c_str()); quit(1); }
     int64_t lonely = 0;
     for (int r = 0; r < n_reads; r++) lonely += !has_record[(size_t)r];
+    if (multi) {
+        std::string rounds;
+        for (int r = 0; r < stretches; r++) rounds += (r ? " + " : "") + std::to_string((long long)per_round[(size_t)r]);
+        printf("overlap: --max-stretches %d: %s candidates per round, %lld merged into clusters, %lld clusters, %lld duplicates dropped\n", stretches, rounds.c_str(), (long long)merged,
+               (long long)n, (long long)duplicates);
+    }
     printf("overlap: %d reads, %lld job(s) in %lld batch(es) over %lld block(s); %lld candidates, %lld mirrored, %lld aligned, %lld written, %lld dropped for asymmetry; index %lld entries (%lld codes dropped by max-occ)\n",
            n_reads, (long long)ost[0], (long long)ost[1], (long long)ost[2], (long long)n_cand, (long long)mirrored, (long long)aligned, (long long)written, (long long)asym, (long long)ost[3],
            (long long)ost[4]);

@@ -589,8 +589,20 @@ int hinge_seed_last_stats(hinge_ctx* ctx, int64_t* out);
  *   more bases (the hit key: b in 23 bits, d in 21, p in 20), more than 2^23 - 1 reads or 2^31 - 1 bases in a block (blocks are
  *   cut so that neither happens), cap too small.  HINGE_E_DEVICE: a failed allocation, or an output slot the kernel did not
  *   write (the outputs are poisoned before every launch).  Jobs run in batches under HINGE_OVERLAP_SCRATCH_MB (256).
- * Not claimed: chaining; a second stretch of the same pair; k-mers of more than max_occ copies per block; reads of 2^20 or more
- *   bases; more than one GPU; parity with DALIGNER's record set.                                                                */
+ * hinge_overlap_run_multi: the same call with up to max_stretches candidates per (a, b, strand), by rounds of
+ *   pick and suppress in k_overlap_vote_multi (overlap_multi_kernels.h).  Every element of a job's sorted hit list starts live.
+ *   In round r the pick of partner b is its LIVE element of the largest cnt (of equal ones the smallest i); a pick of
+ *   cnt >= min_hits is round r's candidate of b, (b, cnt, d, p) of element i + cnt[i] / 2 (live or not).  After the round every
+ *   element of b with d[e] - window < d < d[e] + window is dead (e the picked element; the bounds are exclusive).  cnt is not
+ *   recomputed.  max_partners and TRUNCATED hold per round.  max_stretches: 1..8; 0 = HINGE_OVERLAP_MAX_STRETCHES, else 1;
+ *   anything else is HINGE_E_ARG.  Every value, 1 included, runs k_overlap_vote_multi: at 1 the answer equals hinge_overlap_run's
+ *   value for value.  Everything else - parameters, capacity checks, blocks, batches (a job's output is max_stretches times as
+ *   wide), status, hits, stats, errors - is hinge_overlap_run's.  hinge_overlap_fetch serves either run; the candidates are sorted
+ *   by (aread, bread, comp, round), and hinge_overlap_fetch_round copies every candidate's round (all 0 after hinge_overlap_run).
+ * Not claimed: chaining; a second stretch of the same pair by hinge_overlap_run (hinge_overlap_run_multi: not two stretches on
+ *   one diagonal - less than `window` apart -, not a weaker stretch inside the band a stronger one's alignment settles in, not a
+ *   stretch of fewer than min_hits hits); k-mers of more than max_occ copies per block; reads of 2^20 or more bases; more than
+ *   one GPU; parity with DALIGNER's record set.                                                                                 */
 typedef struct hinge_overlap_params {
     int32_t k, step, window, max_occ, list, max_partners, min_hits, pad;
     int64_t block_bases;
@@ -599,7 +611,10 @@ typedef struct hinge_overlap_params {
 #define HINGE_OVERLAP_MAX_OCC 64
 int hinge_overlap_run(hinge_ctx* ctx, const hinge_overlap_params* params, int32_t* status, int32_t* hits, int64_t* n_out);
 int hinge_overlap_fetch(hinge_ctx* ctx, int64_t cap, hinge_cns_alignment* out, int32_t* count, int32_t* diag, int32_t* rep);
-/* Of the last hinge_overlap_run: out[0] jobs (read, strand, block), [1] batches, [2] blocks, [3] index entries (all blocks), [4] codes
+#define HINGE_OVERLAP_MAX_STRETCHES_LIMIT 8
+int hinge_overlap_run_multi(hinge_ctx* ctx, const hinge_overlap_params* params, int32_t max_stretches, int32_t* status, int32_t* hits, int64_t* n_out);
+int hinge_overlap_fetch_round(hinge_ctx* ctx, int64_t cap, int32_t* round);
+/* Of the last hinge_overlap_run / hinge_overlap_run_multi: out[0] jobs (read, strand, block), [1] batches, [2] blocks, [3] index entries (all blocks), [4] codes
  * dropped by max_occ, [5] OVERFLOW jobs, [6] TRUNCATED jobs, [7] microseconds of the indexes (whichever path built them:
  * hinge_index_last_stats). */
 int hinge_overlap_last_stats(hinge_ctx* ctx, int64_t* out);

@@ -8,9 +8,12 @@ sits in "figures" as {"value": ..., "measured": "gpu" | "host" | "gpu+host" | "n
   kernel's time), trace_local_ms and its records on the first --align candidates (0 = all), records_written (the executable, with
   --cli), recall: the generator's pairs sharing >= 2 000 contig bases (from the reads' longest records on the contigs they were cut
   from) that are candidates after the mirror step.
+--max-stretches S: everything through hinge_overlap_run_multi with S rounds (k_overlap_vote_multi_ms in place of k_overlap_vote_ms,
+candidates_per_round) and `hinge overlap --max-stretches S` with --cli.  --ab N: N interleaved repetitions of hinge_overlap_run and
+hinge_overlap_run_multi at 1, 2 and 4 stretches, each kernel's time by HIP events (vote_kernels_ab_ms: every run and the median).
 There is no reference program for this step here (DALIGNER is not part of the reference tree): no speed-up factor is claimed.
 
-    python tools/overlap_bench.py [--config cns_bench] [--steps 2] [--align 200000] [--cli] [--keep DIR]
+    python tools/overlap_bench.py [--config cns_bench] [--steps 2] [--align 200000] [--cli] [--keep DIR] [--max-stretches S] [--ab N]
 """
 import argparse
 import json
@@ -56,6 +59,8 @@ def main():
     ap.add_argument("--align", type=int, default=200000)
     ap.add_argument("--cli", action="store_true")
     ap.add_argument("--keep", default="")
+    ap.add_argument("--max-stretches", type=int, default=0)
+    ap.add_argument("--ab", type=int, default=0)
     args = ap.parse_args()
     import numpy as np
     import consensus_common as cc
@@ -74,7 +79,10 @@ def main():
     ctx = capi.Context(0)
     capi.Consensus(ctx, os.path.join(wd, "reads"), os.path.join(wd, "reads"))
     t = time.time()
-    pl, count, diag, rep, status, hits = ctx.overlap_run()                               # warm-up (allocations)
+    S = args.max_stretches
+    kernel = "k_overlap_vote_multi" if S else "k_overlap_vote"
+    res = ctx.overlap_run(max_stretches=S)                                               # warm-up (allocations)
+    pl, count, diag, rep, status, hits = res[:6]
     out["first_call_s"] = round(time.time() - t, 3)
     out["stats"] = ctx.overlap_stats()
     out["status"] = {str(s): int(c) for s, c in zip(*np.unique(status, return_counts=True))}
@@ -82,17 +90,21 @@ def main():
     t = time.time()
     index_us = []
     for _ in range(args.steps):
-        ctx.overlap_run()
+        res = ctx.overlap_run(max_stretches=S)
         index_us.append(ctx.overlap_stats()["index_us"])
     ist = ctx.index_last_stats()
     out["index_stats"] = ist
     index_path = "gpu" if ist["host_builds"] == 0 else "host" if ist["device_builds"] == 0 else "gpu+host"
-    call_ms = (time.time() - t) * 1e3 / args.steps
+    call_ms = (time.time() - t) * 1e3 / max(args.steps, 1)
     prof = ctx.profile_report()
-    kernel_ms = prof["k_overlap_vote"][0] / args.steps
-    put("index_ms", round(float(np.mean(index_us)) / 1e3, 3), index_path)
-    put("index_kernels_ms", {k: round(v[0] / args.steps, 3) for k, v in prof.items() if k.startswith("k_index")} if ist["device_builds"] else None, "gpu" if ist["device_builds"] else "not measured")
-    put("k_overlap_vote_ms", round(kernel_ms, 3), "gpu")
+    kernel_ms = prof[kernel][0] / max(args.steps, 1)
+    print("overlap_bench: %d timed call(s) done" % args.steps, file=sys.stderr, flush=True)
+    put("index_ms", round(float(np.mean(index_us)) / 1e3, 3) if index_us else None, index_path if index_us else "not measured")
+    put("index_kernels_ms", {k: round(v[0] / max(args.steps, 1), 3) for k, v in prof.items() if k.startswith("k_index")} if ist["device_builds"] else None, "gpu" if ist["device_builds"] else "not measured")
+    put(kernel + "_ms", round(kernel_ms, 3), "gpu")
+    if S:
+        out["max_stretches"] = S
+        put("candidates_per_round", [int((res[6] == r).sum()) for r in range(S)], "gpu")
     put("run_call_ms", round(call_ms, 3), "host")
     put("candidates", int(len(pl)), "gpu")
     put("candidates_per_s", round(len(pl) / (kernel_ms * 1e-3)) if kernel_ms else None, "gpu")
@@ -112,9 +124,24 @@ def main():
     prof = ctx.profile_report()
     put("trace_local_ms", {"kernels_ms": round(sum(v[0] for k, v in prof.items() if k.startswith("k_trace")), 3), "call_s": round(wall, 3), "candidates": int(len(part)),
                            "of": int(len(sym)), "records": int((st[:, 0] == 0).sum())}, "gpu")
+    if args.ab:
+        runs = {"k_overlap_vote": [], "k_overlap_vote_multi S=1": [], "k_overlap_vote_multi S=2": [], "k_overlap_vote_multi S=4": []}
+        per_round = {}
+        for _ in range(args.ab):
+            for name in runs:
+                s_ab = int(name.split("=")[1]) if "=" in name else 0
+                ctx.profile_enable(4096)
+                res = ctx.overlap_run(max_stretches=s_ab)
+                runs[name].append(round(ctx.profile_report()[name.split()[0]][0], 3))
+                if s_ab:
+                    per_round[name] = [int((res[6] == r).sum()) for r in range(s_ab)]
+            print("overlap_bench: a/b repetition done", file=sys.stderr, flush=True)
+        put("vote_kernels_ab_ms", {k: {"runs": v, "median": float(np.median(v))} for k, v in runs.items()}, "gpu")
+        put("vote_kernels_ab_candidates_per_round", per_round, "gpu")
     if args.cli:
+        print("overlap_bench: the executable", file=sys.stderr, flush=True)
         t = time.time()
-        r = subprocess.run([os.path.join(ROOT, "hinge_amd", "bin", "hinge"), "overlap", "reads", "reads.las"], cwd=wd, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+        r = subprocess.run([os.path.join(ROOT, "hinge_amd", "bin", "hinge"), "overlap", "reads", "reads.las"] + (["--max-stretches", str(S)] if S else []), cwd=wd, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
         assert r.returncode == 0, r.stderr.decode()[-2000:]
         put("records_written", {"summary": r.stdout.decode().strip(), "stderr": r.stderr.decode().strip().splitlines()[-1:], "wall_s": round(time.time() - t, 3)}, "gpu")
     else:
