@@ -5,6 +5,7 @@
 // array of 64 slots between two barriers.
 // stdin: "k max_occ", "n_reads" and the reads (bases as digits 0-3, as stored; "-" = an empty read), "n_ranges" and per range
 // "first end".  stdout per range: "index ENTRIES KEPT DROPPED PASSES", then the lines of codes, gpos and off.
+// Or stdin: "scan LEN SEED MAX_VALUE" - the scan alone, at lengths a whole build would take minutes to reach here (scan_mode).
 #include "index_kernels.h"
 #include "seed_index.h"
 #include <pthread.h>
@@ -90,9 +91,44 @@ static void scan(unsigned* a, long long len, unsigned* sums) {
     launch(std::max(nb, 1ll), [&] { k_index_scan_apply(a, len, nb > 1 ? sums : nullptr); });
 }
 
+// "scan LEN SEED MAX_VALUE": LEN values in [0, MAX_VALUE] through scan() - the real k_index_scan_sums and k_index_scan_apply, the
+// recursion and the carving of the one sums array as index_scan (index_capi.inc) has them - against a serial exclusive scan.
+// stdout: "scan LEN LEVELS SUMS_ELEMS TOTAL".
+static int scan_mode() {
+    long long len;
+    unsigned long long seed;
+    unsigned max_value;
+    std::cin >> len >> seed >> max_value;
+    if (!std::cin || len < 1) { printf("BAD scan arguments\n"); return 2; }
+    Guarded<unsigned> a((size_t)len, 0u), sums((size_t)std::max(sums_elems(len), 1ll), ~0u);
+    std::vector<unsigned> want((size_t)len);
+    unsigned long long x = seed * 0x9e3779b97f4a7c15ull + 0x2545f4914f6cdd1dull, total = 0;
+    for (long long i = 0; i < len; i++) {
+        x ^= x << 13; x ^= x >> 7; x ^= x << 17;                                  // xorshift64
+        const unsigned v = (unsigned)((x >> 20) % ((unsigned long long)max_value + 1ull));
+        a.p()[i] = v;
+        want[(size_t)i] = (unsigned)total;
+        total += v;
+    }
+    if (total >= (1ull << 31)) { printf("BAD scan total %llu\n", total); return 2; }
+    scan(a.p(), len, sums.p());
+    if (!a.ok() || !sums.ok()) { printf("GUARD array\n"); return 4; }
+    if (!lds_ok) { printf("GUARD lds\n"); return 4; }
+    for (long long i = 0; i < len; i++)
+        if (a.p()[i] != want[(size_t)i]) { printf("MISMATCH scan at %lld: %u, not %u\n", i, a.p()[i], want[(size_t)i]); return 6; }
+    int levels = 1;
+    for (long long l = len; l > IDX_SCAN_CHUNK; l = idx_chunks(l)) levels++;
+    printf("scan %lld %d %lld %llu\n", len, levels, sums_elems(len), total);
+    return 0;
+}
+
 int main() {
     int k, max_occ, n_reads, n_ranges;
-    std::cin >> k >> max_occ >> n_reads;
+    std::string word;
+    std::cin >> word;
+    if (word == "scan") return scan_mode();
+    k = std::stoi(word);
+    std::cin >> max_occ >> n_reads;
     std::vector<unsigned char> bps;
     std::vector<int64_t> boff;
     std::vector<int32_t> rlen;

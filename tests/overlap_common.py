@@ -101,19 +101,45 @@ def project(alen, blen, diag, k=K):
     return ab, ae, ab + diag, ae + diag
 
 
+def block_index(reads, first, end, k, max_occ, indexes=None):
+    """seed_common.Index of the block's reads; indexes: a dict that keeps it for the next caller (a block set's takes a second to build)."""
+    key = (first, end, k, max_occ)
+    if indexes is None:
+        return sm.Index(reads[first:end], k, max_occ)
+    if key not in indexes:
+        indexes[key] = sm.Index(reads[first:end], k, max_occ)
+    return indexes[key]
+
+
+def three_blocks(rlen):
+    """A block_bases that cuts the reads into exactly three blocks: a third of the bases and the longest read on top."""
+    bb = sum(rlen) // 3 + max(rlen)
+    assert len(blocks(rlen, bb)) == 3
+    return bb
+
+
 def model_overlap(reads, k=K, step=STEP, window=WINDOW, max_occ=MAX_OCC, list_=LIST, max_partners=MAX_PARTNERS, min_hits=MIN_HITS, block_bases=BLOCK_BASES):
     """What hinge_overlap_run answers: (rows [m][7], count [m], diag [m], rep [m] = (d, p), status [n][2], hits [n][2], stats)."""
-    rlen = [len(r) for r in reads]
     n = len(reads)
-    status = [[NONE, NONE] for _ in range(n)]
-    hits = [[0, 0] for _ in range(n)]
+    rows, cnt, dg, rep, status, hits, st = model_overlap_jobs(reads, range(n), k, step, window, max_occ, list_, max_partners, min_hits, block_bases)
+    return rows, cnt, dg, rep, [status[a] for a in range(n)], [hits[a] for a in range(n)], st
+
+
+def model_overlap_jobs(reads, picks, k=K, step=STEP, window=WINDOW, max_occ=MAX_OCC, list_=LIST, max_partners=MAX_PARTNERS, min_hits=MIN_HITS, block_bases=BLOCK_BASES, indexes=None):
+    """model_overlap for the reads `picks` as a only (against every block, both strands): the rows of those a, status and hits as
+    {a: [forward, complement]}; of the stats, blocks / entries / dropped_codes are the whole call's, jobs / overflow / truncated
+    count the picked jobs.  Every block's index is built once (indexes: block_index's dict)."""
+    rlen = [len(r) for r in reads]
+    picks = sorted(set(int(a) for a in picks))
+    status = {a: [NONE, NONE] for a in picks}
+    hits = {a: [0, 0] for a in picks}
     rows = []
     st = dict(jobs=0, blocks=0, entries=0, dropped_codes=0, overflow=0, truncated=0)
-    Q = [(np.asarray(r, np.uint8), revcomp(r)) for r in reads]
+    Q = {a: (np.asarray(reads[a], np.uint8), revcomp(reads[a])) for a in picks}
     for first, end in blocks(rlen, block_bases):
-        index = sm.Index(reads[first:end], k, max_occ)
+        index = block_index(reads, first, end, k, max_occ, indexes)
         st["blocks"] += 1; st["entries"] += len(index.codes); st["dropped_codes"] += index.dropped_codes
-        for a in range(n):
+        for a in picks:
             for comp in (0, 1):
                 s, nh, cands = job_candidates(index, first, a, Q[a][comp], step, window, list_, max_partners, min_hits)
                 st["jobs"] += 1

@@ -17,7 +17,6 @@ kernel has a bitonic sort, fixed-trip searches, a segmented scan, ballots and de
 import numpy as np
 
 import overlap_common as oc
-import seed_common as sm
 
 NONE, OVERFLOW, TRUNCATED = oc.NONE, oc.OVERFLOW, oc.TRUNCATED
 STRETCHES_MAX = 8
@@ -66,17 +65,26 @@ def job_candidates_multi(index, first, a, Q, step=oc.STEP, window=oc.WINDOW, lis
 def model_overlap_multi(reads, k=oc.K, step=oc.STEP, window=oc.WINDOW, max_occ=oc.MAX_OCC, list_=oc.LIST, max_partners=oc.MAX_PARTNERS, min_hits=oc.MIN_HITS,
                         block_bases=oc.BLOCK_BASES, max_stretches=1):
     """What hinge_overlap_run_multi answers: overlap_common.model_overlap's tuple and, behind it, round [m]; sorted by (a, b, comp, round)."""
-    rlen = [len(r) for r in reads]
     n = len(reads)
-    status = [[NONE, NONE] for _ in range(n)]
-    hits = [[0, 0] for _ in range(n)]
+    rows, cnt, dg, rep, status, hits, st, rnd = model_overlap_multi_jobs(reads, range(n), k, step, window, max_occ, list_, max_partners, min_hits, block_bases, max_stretches)
+    return rows, cnt, dg, rep, [status[a] for a in range(n)], [hits[a] for a in range(n)], st, rnd
+
+
+def model_overlap_multi_jobs(reads, picks, k=oc.K, step=oc.STEP, window=oc.WINDOW, max_occ=oc.MAX_OCC, list_=oc.LIST, max_partners=oc.MAX_PARTNERS, min_hits=oc.MIN_HITS,
+                             block_bases=oc.BLOCK_BASES, max_stretches=1, indexes=None):
+    """model_overlap_multi for the reads `picks` as a only, as overlap_common.model_overlap_jobs: status and hits as
+    {a: [forward, complement]}; every block's index is built once (indexes: overlap_common.block_index's dict)."""
+    rlen = [len(r) for r in reads]
+    picks = sorted(set(int(a) for a in picks))
+    status = {a: [NONE, NONE] for a in picks}
+    hits = {a: [0, 0] for a in picks}
     rows = []
     st = dict(jobs=0, blocks=0, entries=0, dropped_codes=0, overflow=0, truncated=0)
-    Q = [(np.asarray(r, np.uint8), oc.revcomp(r)) for r in reads]
+    Q = {a: (np.asarray(reads[a], np.uint8), oc.revcomp(reads[a])) for a in picks}
     for first, end in oc.blocks(rlen, block_bases):
-        index = sm.Index(reads[first:end], k, max_occ)
+        index = oc.block_index(reads, first, end, k, max_occ, indexes)
         st["blocks"] += 1; st["entries"] += len(index.codes); st["dropped_codes"] += index.dropped_codes
-        for a in range(n):
+        for a in picks:
             for comp in (0, 1):
                 s, nh, rounds = job_candidates_multi(index, first, a, Q[a][comp], step, window, list_, max_partners, min_hits, max_stretches)
                 st["jobs"] += 1

@@ -54,21 +54,8 @@ def _use(ctx, random_set):
 
 
 def _both(ctx, reads, k, max_occ, first=0, n_seqs=None, label=""):
-    """Device build == host build == model, for the range; returns the device build and its stats."""
-    n_seqs = len(reads) - first if n_seqs is None else n_seqs
-    dev = ctx.index_build(first, n_seqs, k, max_occ, where=1)
-    st = ctx.index_last_stats()
-    assert st["device_builds"] == 1 and st["host_builds"] == 0, (label, st)
-    host = ctx.index_build(first, n_seqs, k, max_occ, where=0)
-    sh = ctx.index_last_stats()
-    assert sh["device_builds"] == 0 and sh["host_builds"] == 1, (label, sh)
-    for a, b in zip(dev[:3], host[:3]):
-        assert a.dtype == b.dtype and np.array_equal(a, b), label
-    assert dev[3] == host[3], label
-    want = ic.check(dev, reads[first:first + n_seqs], k, max_occ, label)
-    assert st["entries"] == sh["entries"] == want.all_entries and st["kept"] == sh["kept"] == len(want.codes) and st["dropped_codes"] == want.dropped_codes
-    assert st["passes"] == (2 * k + 7) // 8
-    return dev, st
+    """Device build == host build == model, for the range (index_common.both); returns the device build and its stats."""
+    return ic.both(ctx, reads, k, max_occ, first, n_seqs, label)[:2]
 
 
 def test_entry_counts_around_the_tile(ctx, T, tmp_path):

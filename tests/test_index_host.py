@@ -93,6 +93,24 @@ def test_k16_and_k_values_on_the_host(driver):
         assert _run(driver, reads[:2] + [reads[2][:517]], k, 3, label="k%d" % k)[0][5] == (2 * k + 7) // 8
 
 
+def test_scan_depth_on_the_host(driver):
+    """The scan alone (the driver's "scan" input: the real k_index_scan_sums / k_index_scan_apply and the recursion over the one
+    sums array) at one, two and three levels and at the seams between them - n + 1 == C * C is a second level of exactly one full
+    chunk, C * C + 1 a second level of C + 1 elements and a third of 2, C * C + C + 1 a third of 3 - over flags (0 / 1) and over tile
+    counts (0 .. 300), against a serial exclusive scan inside the program."""
+    C = ic.scan_chunk_from_source()
+    for x, n in enumerate((1, C - 1, C, C + 1, C * C - 1, C * C, C * C + 1, C * C + C + 1)):
+        for max_value in (1, 300):
+            r = subprocess.run([driver], input=("scan %d %d %d\n" % (n, 100 + x, max_value)).encode(), stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+            assert r.returncode == 0, (n, max_value, r.returncode, r.stdout[-300:], r.stderr[-3000:])
+            head = r.stdout.decode().split()
+            assert head[0] == "scan" and int(head[1]) == n and int(head[2]) == ic.scan_levels(n, C) == (1 if n <= C else 2 if n <= C * C else 3)
+            nb1 = -(-n // C)
+            nb2 = -(-nb1 // C)
+            assert int(head[3]) == (0 if n <= C else nb1 if nb1 <= C else nb1 + nb2) and (0 < int(head[4]) < 2 ** 31 or n == 1)
+            assert r.stderr == b""
+
+
 def test_short_reads_and_ranges_on_the_host(driver):
     """Reads shorter than k between longer ones (off and the entry offsets differ); ranges with first > 0, a single-read range and
     a range of short reads only: gpos is relative to the range."""
