@@ -121,6 +121,12 @@ __device__ __forceinline__ unsigned long long ballot_of(bool p) { return __built
 template <typename T> __device__ __forceinline__ T load_at32(const T* p, unsigned byte_off) {
     return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(p) + byte_off);
 }
+// ... of a table the launch only reads, at a uniform offset, through the constant address space: a scalar load wherever it stands
+// (in a loop with atomics and stores the compiler makes a plain load a vector load + v_readfirstlane, uniform address or not)
+template <typename T> __device__ __forceinline__ T load_const_at32(const T* p, unsigned byte_off) {
+    typedef const T __attribute__((address_space(4))) TK;
+    return *(TK*)((unsigned long long)p + byte_off);
+}
 template <typename T> __device__ __forceinline__ void store_at32(T* p, unsigned byte_off, const T& v) {
     *reinterpret_cast<T*>(reinterpret_cast<char*>(p) + byte_off) = v;
 }
@@ -1506,13 +1512,19 @@ __device__ __forceinline__ void k2_q20_body(const int vblock /*the workgroup's i
     for (; (unsigned)item < (unsigned)item_end; item = dyn ? drawn() : item_end) {   // `continue` leaves a read
         if (dyn && lane == 0) grab = atomicAdd(head_ptr, 1u);   // the item after this one
         HINGE_K2_STAMP(0);
-        const int i = load_at32(read_list, (unsigned)item << 2);
+        // With the 16|16 span copy the per-read tables are read through the constant address space: scalar loads.  As plain loads
+        // the compiler makes vector loads + v_readfirstlane of them, uniform offsets or not - the loop's atomics and stores keep it
+        // from proving that nothing writes the tables.  (Nothing does: they are written before the launch.)
+        auto table = [&](auto* p, unsigned byte_off) { return PACKED ? load_const_at32(p, byte_off) : load_at32(p, byte_off); };
+        const int i = table(read_list, (unsigned)item << 2);
         struct Bounds { int64_t s, e; };
-        const Bounds rb = load_at32(reinterpret_cast<const Bounds*>(row_ptr), (unsigned)i << 3);   // row_ptr[i], row_ptr[i + 1]
+        Bounds rb;                                                                                  // row_ptr[i], row_ptr[i + 1]
+        if constexpr (PACKED) rb = Bounds{load_const_at32(row_ptr, (unsigned)i << 3), load_const_at32(row_ptr, ((unsigned)i << 3) + 8u)};
+        else rb = load_at32(reinterpret_cast<const Bounds*>(row_ptr), (unsigned)i << 3);
         const int64_t s = rb.s, e = rb.e;
-        const int rl = load_at32(rlen, (unsigned)i << 2);
-        const int K0 = load_at32(nbins0, (unsigned)i << 2);   // k_cov_stats: bins of the plain profile, or -1 if a coordinate leaves [0, rl]
-        const long long cov_at = COVOUT ? load_at32(cov_off, (unsigned)(i - cov_base) << 3) : 0;   // (fetched with the row bounds, used after phase 1)
+        const int rl = table(rlen, (unsigned)i << 2);
+        const int K0 = table(nbins0, (unsigned)i << 2);   // k_cov_stats: bins of the plain profile, or -1 if a coordinate leaves [0, rl]
+        const long long cov_at = COVOUT ? table(cov_off, (unsigned)(i - cov_base) << 3) : 0;   // (fetched with the row bounds, used after phase 1)
         // (all five look-ups in flight together: left alone the compiler moves the row bounds behind the hand-back test below - a
         // third dependent round trip per read, 69.1 -> 70.3 us)
         asm volatile("" :: "s"(rb.s), "s"(rb.e), "s"(cov_at));
