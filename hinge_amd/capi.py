@@ -127,6 +127,8 @@ SYMBOLS = [
     ("hinge_overlap_run_multi", C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.POINTER(C.c_int64)]),
     ("hinge_overlap_fetch_round", C.c_int, [_VP, C.c_int64, _VP]),
     ("hinge_overlap_last_stats", C.c_int, [_VP, _VP]),
+    ("hinge_overlap_run_tiled", C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.POINTER(C.c_int64)]),
+    ("hinge_overlap_tile_stats", C.c_int, [_VP, _VP]),
     ("hinge_index_build", C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("hinge_index_fetch", C.c_int, [_VP, C.c_int64, _VP, _VP, _VP]),
     ("hinge_index_last_stats", C.c_int, [_VP, _VP]),
@@ -637,7 +639,7 @@ class Context:
         return dict(zip(("jobs", "batches", "entries", "dropped_codes", "overflow", "unplaced", "index_us"), [int(v) for v in st[:7]]))
 
     def overlap_run(self, k: int = 0, step: int = 0, window: int = 0, max_occ: int = 0, list_: int = 0, max_partners: int = 0, min_hits: int = 0, block_bases: int = 0,
-                    max_stretches: int = 0, multi: bool = False):
+                    max_stretches: int = 0, multi: bool = False, tile: int = 0, tiled: bool = False):
         """hinge_overlap_run (`hinge overlap`): read-vs-read overlap candidates of the reads of Consensus(ctx, read_db, read_db) by
         k-mer votes.  0 = the default (HINGE_OVERLAP_*, else 15, 2, 256, 64, 4096, 64, 6, 16 Mi).  Returns (candidates int64 [m, 7] =
         rows of (aread, bread, comp, abpos, aepos, bbpos, bepos) as trace_local takes them, sorted by (aread, bread, comp), count
@@ -645,8 +647,15 @@ class Context:
         else the bits 2 OVERFLOW and 4 TRUNCATED, hits int32 [n, 2] = hits kept) and leaves the call's figures in overlap_stats().
         max_stretches != 0: hinge_overlap_run_multi with that many rounds (1..8): up to that many candidates per (aread, bread,
         comp), sorted by round behind the key; the tuple then ends with round int32 [m].  multi=True takes that entry whatever
-        max_stretches is (0 there: HINGE_OVERLAP_MAX_STRETCHES, else 1)."""
+        max_stretches is (0 there: HINGE_OVERLAP_MAX_STRETCHES, else 1).
+        tile != 0: hinge_overlap_run_tiled with query tiles of that many bases (a power of two 64..8192, at most list * step): the
+        call's step at any read length, reads below 2^30 bases; the tuple is the plain call's, and overlap_tile_stats() has the
+        tile counts.  tiled=True takes that entry whatever tile is (0 there: HINGE_OVERLAP_TILE, else 8192).  Not together with
+        max_stretches / multi (ValueError)."""
         multi = multi or max_stretches != 0
+        tiled = tiled or tile != 0
+        if multi and tiled:
+            raise ValueError("overlap_run: tiles and max_stretches do not go together")
         nr = C.c_int64(0)
         self._ck(self.lib.hinge_seed_db_reads(self.h, C.byref(nr)))
         n = int(nr.value)
@@ -657,6 +666,8 @@ class Context:
         hits = np.zeros((max(n, 1), 2), dtype=np.int32)
         if multi:
             self._ck(self.lib.hinge_overlap_run_multi(self.h, _ptr(params), max_stretches, _ptr(status), _ptr(hits), C.byref(m)))
+        elif tiled:
+            self._ck(self.lib.hinge_overlap_run_tiled(self.h, _ptr(params), tile, _ptr(status), _ptr(hits), C.byref(m)))
         else:
             self._ck(self.lib.hinge_overlap_run(self.h, _ptr(params), _ptr(status), _ptr(hits), C.byref(m)))
         m = m.value
@@ -678,6 +689,13 @@ class Context:
         st = np.zeros(8, np.int64)
         self._ck(self.lib.hinge_overlap_last_stats(self.h, _ptr(st)))
         return dict(zip(("jobs", "batches", "blocks", "entries", "dropped_codes", "overflow", "truncated", "index_us"), [int(v) for v in st[:8]]))
+
+    def overlap_tile_stats(self) -> dict:
+        """Of the last overlap_run: tiles launched, jobs of more than one tile, the largest tile's kept hits, reduce launches (all 0
+        unless the run was tiled)."""
+        st = np.zeros(4, np.int64)
+        self._ck(self.lib.hinge_overlap_tile_stats(self.h, _ptr(st)))
+        return dict(zip(("tiles", "multi_tile_jobs", "max_tile_hits", "reduces"), [int(v) for v in st[:4]]))
 
     def index_build(self, first: int, n_seqs: int, k: int, max_occ: int, where: int = -1):
         """hinge_index_build + hinge_index_fetch: the k-mer index of sequences [first, first + n_seqs) of DB 0 of Consensus(ctx, ...),

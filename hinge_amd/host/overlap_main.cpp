@@ -1,5 +1,5 @@
 // overlap  ==  `hinge overlap READ_DB OUT.las [--k K] [--step S] [--window W] [--max-occ C] [--list L] [--max-partners N] [--min-hits H] [--block-bases B]
-//                              [--max-stretches S] [--min-len M] [--max-err E] [--tspace T] [--band W] [--band-max W]`
+//                              [--max-stretches S] [--tile T] [--min-len M] [--max-err E] [--tspace T] [--band W] [--band-max W]`
 // Not a program of the reference: it stands where the reference's run script calls DALIGNER (HPC.daligner + LAsort / LAmerge) on the
 // read DB against itself to get the read-vs-read .las that `hinge filter` opens.  The candidates - "reads a and b, strand, about this
 // diagonal" - are found by k-mer votes behind the C ABI (hinge_overlap_run, include/hinge_hip.h) and aligned by hinge_trace_local,
@@ -28,6 +28,15 @@
 //   mirror      every kept record's mirror is the same stretch from read b through hinge_trace_run, tied to its origin by index;
 //               a stretch is written only with both records
 //   output      (aread, bread, comp, abpos, bbpos)
+// --tile T (a power of two 64..8192, at most list * step; default HINGE_OVERLAP_TILE; neither: off, the path above call for call):
+//   candidates  hinge_overlap_run_tiled: every query in half-overlapping tiles of T bases, so that a read of any length below 2^30
+//               bases is sampled at --step (without it a read's step grows until it has at most --list positions, and a read of
+//               2^20 or more bases is refused); everything behind the candidates is the path above
+//   alignment   a record of a read of more than one tile that begins or ends inside both reads - the box along a tile's diagonal cut
+//               it - runs through hinge_trace_local once more from its own end points with room for 1024 bases per side; the longer
+//               of the two stays
+//   Not together with --max-stretches above 1 (the usage, exit 1).  Not claimed: that the alignment of a placement of 2^20 or
+//   more bases succeeds - the option lifts the limit of the candidate search.
 // Not claimed: two stretches on one diagonal; a weaker stretch inside the band that a stronger one's alignment settles in (after a
 // TOUCHED widening both boxes may return the same optimum: the duplicate rule then leaves one); stretches of fewer than min-hits hits.
 #include "host_common.h"
@@ -38,9 +47,11 @@ using namespace hh;
 
 static void usage() {
     fprintf(stderr, "usage: overlap <read db> <out.las> [--k K] [--step S] [--window W] [--max-occ C] [--list L] [--max-partners N] [--min-hits H] [--block-bases B]\n"
-                    "               [--max-stretches S] [--min-len M] [--max-err E] [--tspace T] [--band W] [--band-max W]\n"
+                    "               [--max-stretches S] [--tile T] [--min-len M] [--max-err E] [--tspace T] [--band W] [--band-max W]\n"
                     "       read-vs-read overlaps of <read db> by k-mer votes and banded local alignment, as the .las `hinge filter` reads\n"
-                    "       --max-stretches S: up to S (1..8) records per (aread, bread, strand), one per stretch; default HINGE_OVERLAP_MAX_STRETCHES, else 1\n");
+                    "       --max-stretches S: up to S (1..8) records per (aread, bread, strand), one per stretch; default HINGE_OVERLAP_MAX_STRETCHES, else 1\n"
+                    "       --tile T: the candidates of every read from half-overlapping query tiles of T bases (a power of two 64..8192, at most list * step):\n"
+                    "                 reads of any length below 2^30 bases at --step; default HINGE_OVERLAP_TILE, else off; not with --max-stretches above 1\n");
 }
 
 // both reads whole along the record-frame diagonal (bbpos - abpos), clamped to both; the rule of overlap_project (overlap_kernels.h)
@@ -51,6 +62,8 @@ static bool along(int alen, int blen, long long diag, int k, hinge_cns_alignment
     return true;
 }
 
+constexpr int TILE_EXTEND = 1024;     // --tile: the room per side of a record's second run (the widest default band: a diagonal further off is not followed anyway)
+
 static inline uint64_t pair_key(int a, int b, int comp) { return ((uint64_t)(uint32_t)a << 33) | ((uint64_t)(uint32_t)b << 1) | (uint64_t)(comp & 1); }
 
 int main(int argc, char* argv[]) {
@@ -60,6 +73,7 @@ int main(int argc, char* argv[]) {
     int min_len = 1000, tspace = 100, band = 0, band_max = 0;
     double max_err = 0.30;
     int stretches = 0;                              // 0: not given
+    int tile = 0;                                   // 0: not given
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto text = [&](const char* name) -> const char* {
@@ -83,6 +97,7 @@ int main(int argc, char* argv[]) {
             stretches = (int)val("--max-stretches");
             if (stretches > HINGE_OVERLAP_MAX_STRETCHES_LIMIT) { fprintf(stderr, "overlap: --max-stretches needs a number in 1..8\n"); usage(); return 1; }
         }
+        else if (a == "--tile") tile = (int)val("--tile");
         else if (a == "--min-len") min_len = (int)val("--min-len");
         else if (a == "--tspace") tspace = (int)val("--tspace");
         else if (a == "--band") band = (int)val("--band");
@@ -103,6 +118,13 @@ int main(int argc, char* argv[]) {
         if (stretches < 1 || stretches > HINGE_OVERLAP_MAX_STRETCHES_LIMIT) { fprintf(stderr, "overlap: HINGE_OVERLAP_MAX_STRETCHES needs a number in 1..8\n"); usage(); return 1; }
     }
     const bool multi = stretches > 1;
+    if (tile == 0) {
+        const char* g = getenv("HINGE_OVERLAP_TILE");
+        if (g && *g) tile = atoi(g);
+        if (g && *g && tile < 1) { fprintf(stderr, "overlap: HINGE_OVERLAP_TILE needs a power of two in 64..8192\n"); usage(); return 1; }
+    }
+    if (tile != 0 && (tile < 64 || tile > HINGE_OVERLAP_TILE_MAX || (tile & (tile - 1)))) { fprintf(stderr, "overlap: --tile needs a power of two in 64..8192\n"); usage(); return 1; }
+    if (tile != 0 && multi) { fprintf(stderr, "overlap: --tile and --max-stretches above 1 do not go together\n"); usage(); return 1; }
     PhaseTimer tm("overlap");
     CtxInit gpu;
     gpu.start();
@@ -123,7 +145,9 @@ int main(int argc, char* argv[]) {
     // ---- the candidates, made symmetric ------------------------------------------------------------------------------------------
     std::vector<int32_t> jstatus((size_t)std::max(2 * n_reads, 2));
     int64_t n_cand = 0;
-    if ((multi ? hinge_overlap_run_multi(ctx, &prm, stretches, jstatus.data(), nullptr, &n_cand) : hinge_overlap_run(ctx, &prm, jstatus.data(), nullptr, &n_cand)) != HINGE_OK) die("votes");
+    if ((multi ? hinge_overlap_run_multi(ctx, &prm, stretches, jstatus.data(), nullptr, &n_cand)
+         : tile ? hinge_overlap_run_tiled(ctx, &prm, tile, jstatus.data(), nullptr, &n_cand)
+                : hinge_overlap_run(ctx, &prm, jstatus.data(), nullptr, &n_cand)) != HINGE_OK) die("votes");
     std::vector<hinge_cns_alignment> cand((size_t)std::max<int64_t>(n_cand, 1));
     std::vector<int32_t> count((size_t)std::max<int64_t>(n_cand, 1)), diag((size_t)std::max<int64_t>(n_cand, 1));
     if (hinge_overlap_fetch(ctx, n_cand, cand.data(), count.data(), diag.data(), nullptr) != HINGE_OK) die("votes");
@@ -136,6 +160,8 @@ int main(int argc, char* argv[]) {
     }
     int64_t ost[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     (void)hinge_overlap_last_stats(ctx, ost);
+    int64_t tst[4] = {0, 0, 0, 0};
+    if (tile) (void)hinge_overlap_tile_stats(ctx, tst);
     tm.mark("index + votes");
     const int k = prm.k ? prm.k : (getenv("HINGE_OVERLAP_K") && *getenv("HINGE_OVERLAP_K") ? atoi(getenv("HINGE_OVERLAP_K")) : 15);
     const int window = prm.window ? prm.window : (getenv("HINGE_OVERLAP_WINDOW") && *getenv("HINGE_OVERLAP_WINDOW") ? atoi(getenv("HINGE_OVERLAP_WINDOW")) : 256);
@@ -216,12 +242,13 @@ int main(int argc, char* argv[]) {
         return x.comp < y.comp;
     };
     // one round: `in` (sorted by A read) through hinge_trace_local (local) or hinge_trace_run; what stays goes to `kept`, the rest is counted
-    auto align_round = [&](const std::vector<hinge_cns_alignment>& in, bool local, int64_t& dropped) {
+    // ends / rm: hinge_trace_local's end rule and the room it may add per side (nullptr: the library's, `room`)
+    auto align_round = [&](const std::vector<hinge_cns_alignment>& in, bool local, int64_t& dropped, const hinge_trace_ends* ends = nullptr, int rm_given = -1) {
         std::vector<hinge_cns_alignment> out;
         std::vector<uint16_t> trace;
         std::vector<int32_t> diffs, status, score;
         const int64_t n_in = (int64_t)in.size();
-        const int rm = local ? room : 0;
+        const int rm = !local ? 0 : rm_given >= 0 ? rm_given : room;
         for (int64_t x0 = 0; x0 < n_in;) {
             int64_t x1 = std::min(n_in, x0 + chunk_records);
             while (x1 < n_in && in[(size_t)x1].aread == in[(size_t)x1 - 1].aread) x1++;        // whole A reads
@@ -230,7 +257,7 @@ int main(int argc, char* argv[]) {
             for (int64_t x = x0; x < x1; x++) cap += 2 * (int64_t)((in[(size_t)x].aepos + rm - 1) / tspace - std::max(in[(size_t)x].abpos - rm, 0) / tspace + 1);
             out.resize((size_t)m); trace.resize((size_t)std::max<int64_t>(cap, 1)); diffs.resize((size_t)m); status.resize((size_t)(2 * m)); score.resize((size_t)m);
             int64_t n_trace = 0;
-            const int rc = local ? hinge_trace_local(ctx, m, in.data() + x0, tspace, band, band_max, nullptr, out.data(), trace.data(), cap, &n_trace, diffs.data(), status.data(), score.data())
+            const int rc = local ? hinge_trace_local(ctx, m, in.data() + x0, tspace, band, band_max, ends, out.data(), trace.data(), cap, &n_trace, diffs.data(), status.data(), score.data())
                                  : hinge_trace_run(ctx, m, in.data() + x0, tspace, band, band_max, out.data(), trace.data(), cap, &n_trace, diffs.data(), status.data());
             if (rc != HINGE_OK) die("trace");
             for (int64_t x = 0; x < m; x++) {
@@ -249,6 +276,47 @@ int main(int argc, char* argv[]) {
         if (r.aread < r.bread) first.push_back(r);
     int64_t unaligned = 0, duplicates = 0;
     align_round(first, true, unaligned);
+    int64_t reextended = 0;
+    if (tile) {
+        // ---- --tile: a tile's diagonal is that of 8 kb of the query, and the box - both reads whole along it - cuts an end whose own
+        //      diagonal lies on its far side: the record then begins (ends) inside BOTH reads.  Such a record of a read of more than one
+        //      tile runs again from its own end points with room for TILE_EXTEND bases per side (reads of one tile: nothing changes) ------
+        std::vector<hinge_cns_alignment> again;
+        std::vector<size_t> again_of;
+        auto tiles_of = [&](int r) { return (long long)db.rlen[(size_t)r] - k + 1 > tile; };
+        for (size_t x = 0; x < kept.size(); x++) {
+            const hinge_cns_alignment& r = kept[x].r;
+            const int alen = db.rlen[(size_t)r.aread], blen = db.rlen[(size_t)r.bread];
+            if (!(tiles_of(r.aread) || tiles_of(r.bread))) continue;
+            if (std::min(r.abpos, r.bbpos) == 0 && std::min(alen - r.aepos, blen - r.bepos) == 0) continue;
+            hinge_cns_alignment m = r;
+            m.tlen = 0; m.trace_off = 0;
+            again.push_back(m);
+            again_of.push_back(x);
+        }
+        if (!again.empty()) {
+            std::vector<Kept> k1;
+            std::vector<uint16_t> t1;
+            k1.swap(kept); t1.swap(ktrace);
+            const int64_t aligned1 = aligned;
+            int64_t not_better = 0;
+            hinge_trace_ends e;
+            e.extend = TILE_EXTEND; e.match = 0; e.diff = 0; e.min_score = 0;
+            align_round(again, true, not_better, &e, TILE_EXTEND);
+            aligned = aligned1;
+            for (const Kept& q : kept) {                // (a record the second run dropped stays as the first run left it)
+                Kept& o = k1[again_of[(size_t)q.origin]];
+                if (q.r.aepos - q.r.abpos < o.r.aepos - o.r.abpos) continue;
+                const int64_t origin = o.origin;
+                o = q;
+                o.origin = origin;
+                o.toff = (int64_t)t1.size();
+                t1.insert(t1.end(), ktrace.begin() + q.toff, ktrace.begin() + q.toff + q.r.tlen);
+                reextended++;
+            }
+            kept.swap(k1); ktrace.swap(t1);
+        }
+    }
     if (multi) {
         // ---- duplicates: per key in the order (A length descending, abpos, bbpos), against the records already kept ------------------
         std::sort(kept.begin(), kept.end(), [&](const Kept& x, const Kept& y) {
@@ -357,6 +425,9 @@ int main(int argc, char* argv[]) {
         printf("overlap: --max-stretches %d: %s candidates per round, %lld merged into clusters, %lld clusters, %lld duplicates dropped\n", stretches, rounds.c_str(), (long long)merged,
                (long long)n, (long long)duplicates);
     }
+    if (tile)
+        printf("overlap: --tile %d: %lld tile(s), %lld job(s) of more than one, the largest tile kept %lld hit(s), %lld reduce launch(es); %lld record(s) extended by a second run\n", tile, (long long)tst[0], (long long)tst[1],
+               (long long)tst[2], (long long)tst[3], (long long)reextended);
     printf("overlap: %d reads, %lld job(s) in %lld batch(es) over %lld block(s); %lld candidates, %lld mirrored, %lld aligned, %lld written, %lld dropped for asymmetry; index %lld entries (%lld codes dropped by max-occ)\n",
            n_reads, (long long)ost[0], (long long)ost[1], (long long)ost[2], (long long)n_cand, (long long)mirrored, (long long)aligned, (long long)written, (long long)asym, (long long)ost[3],
            (long long)ost[4]);

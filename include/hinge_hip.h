@@ -599,6 +599,22 @@ int hinge_seed_last_stats(hinge_ctx* ctx, int64_t* out);
  *   value for value.  Everything else - parameters, capacity checks, blocks, batches (a job's output is max_stretches times as
  *   wide), status, hits, stats, errors - is hinge_overlap_run's.  hinge_overlap_fetch serves either run; the candidates are sorted
  *   by (aread, bread, comp, round), and hinge_overlap_fetch_round copies every candidate's round (all 0 after hinge_overlap_run).
+ * hinge_overlap_run_tiled: the same call with every query cut into half-overlapping tiles, for reads of any
+ *   length below 2^30 bases at the call's own step (hinge_overlap_run widens a read's step until it has at most `list` sampled
+ *   positions, and refuses reads of 2^20 or more bases).  tile T: a power of two 64..HINGE_OVERLAP_TILE_MAX with T <= list * step;
+ *   0 = HINGE_OVERLAP_TILE, else 8192; anything else is HINGE_E_ARG.  The sampled positions are the read's p = j * step <= alen - k;
+ *   tile t of a (read, strand) holds those with t T/2 <= p < t T/2 + T; one tile if alen - k + 1 <= T, else
+ *   ceil((alen - k + 1 - T) / (T/2)) + 1.  Every tile is a job of hinge_overlap_run's rule (k_overlap_vote_tile,
+ *   overlap_tile_kernels.h; d in the whole read's frame; the hit key: b in 20 bits, d in 31, p - t T/2 in 13).  Per (read, strand,
+ *   block) k_overlap_tile_reduce keeps per b the tile candidate of the largest cnt, of equal ones the lowest tile's, in ascending
+ *   b, the first max_partners; status NONE without a candidate, else OVERFLOW if any tile dropped hits and TRUNCATED if any tile
+ *   was or more than max_partners partners remain; hits = the sum of the tiles' kept hits.  A read of one tile gets
+ *   hinge_overlap_run's answer value for value.  HINGE_E_CAPACITY (before any launch): a read of 2^30 or more bases, a read whose
+ *   tile rows take 2^31 or more ints; blocks are cut at 2^20 - 1 reads.  Batches go by tile count under
+ *   HINGE_OVERLAP_SCRATCH_MB; a job's tiles stay in one batch.  hinge_overlap_fetch, hinge_overlap_fetch_round (all 0) and
+ *   hinge_overlap_last_stats serve it as they serve hinge_overlap_run.  hinge_overlap_tile_stats: out[0] tiles launched, [1] jobs
+ *   of more than one tile, [2] the largest tile's kept hits, [3] reduce launches (all 0 after the other two calls).
+ *   Not claimed for it: tiles together with max_stretches; that hinge_trace_local aligns a placement of 2^20 or more bases.
  * Not claimed: chaining; a second stretch of the same pair by hinge_overlap_run (hinge_overlap_run_multi: not two stretches on
  *   one diagonal - less than `window` apart -, not a weaker stretch inside the band a stronger one's alignment settles in, not a
  *   stretch of fewer than min_hits hits); k-mers of more than max_occ copies per block; reads of 2^20 or more bases; more than
@@ -614,6 +630,9 @@ int hinge_overlap_fetch(hinge_ctx* ctx, int64_t cap, hinge_cns_alignment* out, i
 #define HINGE_OVERLAP_MAX_STRETCHES_LIMIT 8
 int hinge_overlap_run_multi(hinge_ctx* ctx, const hinge_overlap_params* params, int32_t max_stretches, int32_t* status, int32_t* hits, int64_t* n_out);
 int hinge_overlap_fetch_round(hinge_ctx* ctx, int64_t cap, int32_t* round);
+#define HINGE_OVERLAP_TILE_MAX 8192
+int hinge_overlap_run_tiled(hinge_ctx* ctx, const hinge_overlap_params* params, int32_t tile, int32_t* status, int32_t* hits, int64_t* n_out);
+int hinge_overlap_tile_stats(hinge_ctx* ctx, int64_t* out);
 /* Of the last hinge_overlap_run / hinge_overlap_run_multi: out[0] jobs (read, strand, block), [1] batches, [2] blocks, [3] index entries (all blocks), [4] codes
  * dropped by max_occ, [5] OVERFLOW jobs, [6] TRUNCATED jobs, [7] microseconds of the indexes (whichever path built them:
  * hinge_index_last_stats). */

@@ -11,9 +11,13 @@ sits in "figures" as {"value": ..., "measured": "gpu" | "host" | "gpu+host" | "n
 --max-stretches S: everything through hinge_overlap_run_multi with S rounds (k_overlap_vote_multi_ms in place of k_overlap_vote_ms,
 candidates_per_round) and `hinge overlap --max-stretches S` with --cli.  --ab N: N interleaved repetitions of hinge_overlap_run and
 hinge_overlap_run_multi at 1, 2 and 4 stretches, each kernel's time by HIP events (vote_kernels_ab_ms: every run and the median).
+--tile T: everything through hinge_overlap_run_tiled with query tiles of T bases (k_overlap_vote_tile_ms and
+k_overlap_tile_reduce_ms in place of k_overlap_vote_ms, tile_stats) and `hinge overlap --tile T` with --cli; with --ab N: N
+interleaved repetitions of hinge_overlap_run and hinge_overlap_run_tiled, each kernel's time by HIP events (tile_ab_ms: every run, the
+medians and the ratio of the tiled kernels' time to k_overlap_vote's).
 There is no reference program for this step here (DALIGNER is not part of the reference tree): no speed-up factor is claimed.
 
-    python tools/overlap_bench.py [--config cns_bench] [--steps 2] [--align 200000] [--cli] [--keep DIR] [--max-stretches S] [--ab N]
+    python tools/overlap_bench.py [--config cns_bench] [--steps 2] [--align 200000] [--cli] [--keep DIR] [--max-stretches S] [--ab N] [--tile T]
 """
 import argparse
 import json
@@ -61,6 +65,7 @@ def main():
     ap.add_argument("--keep", default="")
     ap.add_argument("--max-stretches", type=int, default=0)
     ap.add_argument("--ab", type=int, default=0)
+    ap.add_argument("--tile", type=int, default=0)
     args = ap.parse_args()
     import numpy as np
     import consensus_common as cc
@@ -80,8 +85,10 @@ def main():
     capi.Consensus(ctx, os.path.join(wd, "reads"), os.path.join(wd, "reads"))
     t = time.time()
     S = args.max_stretches
-    kernel = "k_overlap_vote_multi" if S else "k_overlap_vote"
-    res = ctx.overlap_run(max_stretches=S)                                               # warm-up (allocations)
+    T = args.tile
+    assert not (S and T), "--tile and --max-stretches do not go together"
+    kernel = "k_overlap_vote_multi" if S else "k_overlap_vote_tile" if T else "k_overlap_vote"
+    res = ctx.overlap_run(max_stretches=S, tile=T)                                               # warm-up (allocations)
     pl, count, diag, rep, status, hits = res[:6]
     out["first_call_s"] = round(time.time() - t, 3)
     out["stats"] = ctx.overlap_stats()
@@ -90,7 +97,7 @@ def main():
     t = time.time()
     index_us = []
     for _ in range(args.steps):
-        res = ctx.overlap_run(max_stretches=S)
+        res = ctx.overlap_run(max_stretches=S, tile=T)
         index_us.append(ctx.overlap_stats()["index_us"])
     ist = ctx.index_last_stats()
     out["index_stats"] = ist
@@ -102,6 +109,10 @@ def main():
     put("index_ms", round(float(np.mean(index_us)) / 1e3, 3) if index_us else None, index_path if index_us else "not measured")
     put("index_kernels_ms", {k: round(v[0] / max(args.steps, 1), 3) for k, v in prof.items() if k.startswith("k_index")} if ist["device_builds"] else None, "gpu" if ist["device_builds"] else "not measured")
     put(kernel + "_ms", round(kernel_ms, 3), "gpu")
+    if T:
+        out["tile"] = T
+        out["tile_stats"] = ctx.overlap_tile_stats()
+        put("k_overlap_tile_reduce_ms", round(prof["k_overlap_tile_reduce"][0] / max(args.steps, 1), 3), "gpu")
     if S:
         out["max_stretches"] = S
         put("candidates_per_round", [int((res[6] == r).sum()) for r in range(S)], "gpu")
@@ -124,7 +135,21 @@ def main():
     prof = ctx.profile_report()
     put("trace_local_ms", {"kernels_ms": round(sum(v[0] for k, v in prof.items() if k.startswith("k_trace")), 3), "call_s": round(wall, 3), "candidates": int(len(part)),
                            "of": int(len(sym)), "records": int((st[:, 0] == 0).sum())}, "gpu")
-    if args.ab:
+    if args.ab and T:
+        runs = {"k_overlap_vote": [], "k_overlap_vote_tile": [], "k_overlap_tile_reduce": []}
+        for _ in range(args.ab):
+            ctx.profile_enable(4096)
+            ctx.overlap_run()
+            runs["k_overlap_vote"].append(round(ctx.profile_report()["k_overlap_vote"][0], 3))
+            ctx.profile_enable(4096)
+            ctx.overlap_run(tile=T)
+            rp = ctx.profile_report()
+            runs["k_overlap_vote_tile"].append(round(rp["k_overlap_vote_tile"][0], 3))
+            runs["k_overlap_tile_reduce"].append(round(rp["k_overlap_tile_reduce"][0], 3))
+            print("overlap_bench: a/b repetition done", file=sys.stderr, flush=True)
+        med = {k: float(np.median(v)) for k, v in runs.items()}
+        put("tile_ab_ms", {"runs": runs, "median": med, "tiled_over_plain": round((med["k_overlap_vote_tile"] + med["k_overlap_tile_reduce"]) / med["k_overlap_vote"], 3)}, "gpu")
+    elif args.ab:
         runs = {"k_overlap_vote": [], "k_overlap_vote_multi S=1": [], "k_overlap_vote_multi S=2": [], "k_overlap_vote_multi S=4": []}
         per_round = {}
         for _ in range(args.ab):
@@ -141,7 +166,7 @@ def main():
     if args.cli:
         print("overlap_bench: the executable", file=sys.stderr, flush=True)
         t = time.time()
-        r = subprocess.run([os.path.join(ROOT, "hinge_amd", "bin", "hinge"), "overlap", "reads", "reads.las"] + (["--max-stretches", str(S)] if S else []), cwd=wd, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+        r = subprocess.run([os.path.join(ROOT, "hinge_amd", "bin", "hinge"), "overlap", "reads", "reads.las"] + (["--max-stretches", str(S)] if S else []) + (["--tile", str(T)] if T else []), cwd=wd, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
         assert r.returncode == 0, r.stderr.decode()[-2000:]
         put("records_written", {"summary": r.stdout.decode().strip(), "stderr": r.stderr.decode().strip().splitlines()[-1:], "wall_s": round(time.time() - t, 3)}, "gpu")
     else:
