@@ -129,6 +129,7 @@ SYMBOLS = [
     ("hinge_overlap_last_stats", C.c_int, [_VP, _VP]),
     ("hinge_overlap_run_tiled", C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.POINTER(C.c_int64)]),
     ("hinge_overlap_tile_stats", C.c_int, [_VP, _VP]),
+    ("hinge_overlap_run_tiled_multi", C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, C.POINTER(C.c_int64)]),
     ("hinge_index_build", C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("hinge_index_fetch", C.c_int, [_VP, C.c_int64, _VP, _VP, _VP]),
     ("hinge_index_last_stats", C.c_int, [_VP, _VP]),
@@ -639,7 +640,7 @@ class Context:
         return dict(zip(("jobs", "batches", "entries", "dropped_codes", "overflow", "unplaced", "index_us"), [int(v) for v in st[:7]]))
 
     def overlap_run(self, k: int = 0, step: int = 0, window: int = 0, max_occ: int = 0, list_: int = 0, max_partners: int = 0, min_hits: int = 0, block_bases: int = 0,
-                    max_stretches: int = 0, multi: bool = False, tile: int = 0, tiled: bool = False):
+                    max_stretches: int = 0, multi: bool = False, tile: int = 0, tiled: bool = False, tile_stretches: int = 0, tiled_multi: bool = False):
         """hinge_overlap_run (`hinge overlap`): read-vs-read overlap candidates of the reads of Consensus(ctx, read_db, read_db) by
         k-mer votes.  0 = the default (HINGE_OVERLAP_*, else 15, 2, 256, 64, 4096, 64, 6, 16 Mi).  Returns (candidates int64 [m, 7] =
         rows of (aread, bread, comp, abpos, aepos, bbpos, bepos) as trace_local takes them, sorted by (aread, bread, comp), count
@@ -651,11 +652,20 @@ class Context:
         tile != 0: hinge_overlap_run_tiled with query tiles of that many bases (a power of two 64..8192, at most list * step): the
         call's step at any read length, reads below 2^30 bases; the tuple is the plain call's, and overlap_tile_stats() has the
         tile counts.  tiled=True takes that entry whatever tile is (0 there: HINGE_OVERLAP_TILE, else 8192).  Not together with
-        max_stretches / multi (ValueError)."""
+        max_stretches / multi (ValueError).
+        tile_stretches != 0 (with tile or tiled): hinge_overlap_run_tiled_multi, tiles with up to that many candidates (1..8) per
+        (aread, bread, comp); the tuple ends with round int32 [m] as with max_stretches.  tiled_multi=True takes that entry whatever
+        tile_stretches and tile are (0 there: HINGE_OVERLAP_TILE_STRETCHES, else 1; HINGE_OVERLAP_TILE, else 8192).  ValueError
+        for tile_stretches without a tile, or together with max_stretches / multi."""
         multi = multi or max_stretches != 0
         tiled = tiled or tile != 0
         if multi and tiled:
             raise ValueError("overlap_run: tiles and max_stretches do not go together")
+        tiled = tiled or tiled_multi
+        if (tile_stretches != 0 or tiled_multi) and multi:
+            raise ValueError("overlap_run: tile_stretches and max_stretches do not go together")
+        if tile_stretches != 0 and not tiled:
+            raise ValueError("overlap_run: tile_stretches needs a tile")
         nr = C.c_int64(0)
         self._ck(self.lib.hinge_seed_db_reads(self.h, C.byref(nr)))
         n = int(nr.value)
@@ -664,7 +674,10 @@ class Context:
         params[0] = (k, step, window, max_occ, list_, max_partners, min_hits, 0, block_bases)
         m = C.c_int64(0)
         hits = np.zeros((max(n, 1), 2), dtype=np.int32)
-        if multi:
+        tiled_multi = tiled_multi or tile_stretches != 0
+        if tiled_multi:
+            self._ck(self.lib.hinge_overlap_run_tiled_multi(self.h, _ptr(params), tile, tile_stretches, _ptr(status), _ptr(hits), C.byref(m)))
+        elif multi:
             self._ck(self.lib.hinge_overlap_run_multi(self.h, _ptr(params), max_stretches, _ptr(status), _ptr(hits), C.byref(m)))
         elif tiled:
             self._ck(self.lib.hinge_overlap_run_tiled(self.h, _ptr(params), tile, _ptr(status), _ptr(hits), C.byref(m)))
@@ -677,7 +690,7 @@ class Context:
         rep = np.zeros((max(m, 1), 2), dtype=np.int32)
         self._ck(self.lib.hinge_overlap_fetch(self.h, m, _ptr(out), _ptr(count), _ptr(diag), _ptr(rep)))
         pl = np.stack([out[name][:m].astype(np.int64) for name in ("aread", "bread", "comp", "abpos", "aepos", "bbpos", "bepos")], axis=1) if m else np.zeros((0, 7), np.int64)
-        if multi:
+        if multi or tiled_multi:
             rnd = np.zeros(max(m, 1), dtype=np.int32)
             self._ck(self.lib.hinge_overlap_fetch_round(self.h, m, _ptr(rnd)))
             return pl, count[:m], diag[:m], rep[:m], status[:n], hits[:n], rnd[:m]

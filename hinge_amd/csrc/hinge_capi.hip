@@ -23,6 +23,7 @@
 #include "overlap_kernels.h"
 #include "overlap_multi_kernels.h"
 #include "overlap_tile_kernels.h"
+#include "overlap_tile_multi_kernels.h"
 #include "index_kernels.h"
 
 using namespace hinge;
@@ -175,11 +176,11 @@ struct hinge_ctx {
 
 enum KernelId { KID_STATS = 0, KID_MEDIAN, KID_MASK_ANNOTATE, KID_MASK_FALLBACK, KID_HINGE_COUNT, KID_HINGE_CALL, KID_HINGE_EXACT, KID_COVERAGE_BINS, KID_TRIM_CLASSIFY,
                 KID_PILEUP_FACTS, KID_MATCHING_POSITION, KID_SELECT_EDGES, KID_SPEC_PREDICT, KID_MASK_FINAL, KID_CNS_REALIGN, KID_CNS_COLUMNS, KID_CNS_VOTE, KID_CNS_CALL, KID_DRAFT_ALIGN, KID_DRAFT_CNS, KID_DRAFT_ALIGN_LONG, KID_DRAFT_CNS_DEEP, KID_MASK_LONG, KID_TRACE_FILL, KID_TRACE_WALK, KID_TRACE_CLIP, KID_TRACE_FILL_LOCAL, KID_TRACE_WALK_LOCAL, KID_SEED_VOTE, KID_EXACT_BEGIN, KID_OVERLAP_VOTE, KID_INDEX_EXTRACT, KID_INDEX_HIST,
-                KID_INDEX_SCAN, KID_INDEX_SCATTER, KID_INDEX_FLAG, KID_INDEX_COMPACT, KID_OVERLAP_VOTE_MULTI, KID_OVERLAP_VOTE_TILE, KID_OVERLAP_TILE_REDUCE, KID_COUNT };
+                KID_INDEX_SCAN, KID_INDEX_SCATTER, KID_INDEX_FLAG, KID_INDEX_COMPACT, KID_OVERLAP_VOTE_MULTI, KID_OVERLAP_VOTE_TILE, KID_OVERLAP_TILE_REDUCE, KID_OVERLAP_VOTE_TILE_MULTI, KID_OVERLAP_TILE_REDUCE_MULTI, KID_COUNT };
 static const char* const KERNEL_NAMES[KID_COUNT] = {"k_cov_stats", "k_median_hist", "k_mask_annotate", "k_mask_annotate_fallback", "k_hinge_count", "k_hinge_call", "k_hinge_exact",
                                                      "k_coverage_bins", "k_trim_classify", "k_pileup_facts", "k_matching_position", "k_select_edges", "k_spec_predict",
                                                      "k_mask_annotate_final", "k_cns_realign", "k_cns_columns", "k_cns_vote", "k_cns_call", "k_draft_align", "k_draft_cns", "k_draft_align_long", "k_draft_cns_deep", "k_mask_annotate_long", "k_trace_fill", "k_trace_walk", "k_trace_clip", "k_trace_fill_local", "k_trace_walk_local", "k_seed_vote", "k_exact_begin", "k_overlap_vote", "k_index_extract", "k_index_hist",
-                                                     "k_index_scan", "k_index_scatter", "k_index_flag", "k_index_compact", "k_overlap_vote_multi", "k_overlap_vote_tile", "k_overlap_tile_reduce"};
+                                                     "k_index_scan", "k_index_scatter", "k_index_flag", "k_index_compact", "k_overlap_vote_multi", "k_overlap_vote_tile", "k_overlap_tile_reduce", "k_overlap_vote_tile_multi", "k_overlap_tile_reduce_multi"};
 
 struct ProfScope {
     hinge_ctx* c;

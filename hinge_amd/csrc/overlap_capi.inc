@@ -4,7 +4,8 @@
 // jobs (two per read) in batches under the scratch budget against every block, a candidate's projection in the record's frame
 // (overlap_project) and the order of the result.  The kernels: overlap_kernels.h (one candidate per (a, b, strand)) and
 // overlap_multi_kernels.h (hinge_overlap_run_multi: up to max_stretches of them); overlap_tile_kernels.h (hinge_overlap_run_tiled: the
-// query in half-overlapping tiles, a reduce per job; DESIGN.md 3.14).  All entry points are overlap_run_impl.
+// query in half-overlapping tiles, a reduce per job; DESIGN.md 3.14); overlap_tile_multi_kernels.h (hinge_overlap_run_tiled_multi: tiles
+// with up to max_stretches candidates per pair; DESIGN.md 3.15).  All entry points are overlap_run_impl.
 
 static_assert(OVL_STRETCHES_MAX == HINGE_OVERLAP_MAX_STRETCHES_LIMIT, "the header's limit is the kernel's");
 static_assert(OVT_TILE_MAX == HINGE_OVERLAP_TILE_MAX, "the header's limit is the kernel's");
@@ -56,7 +57,9 @@ static int overlap_batch(hinge_ctx* ctx, const OvlJob* jobs, size_t nj, const Ov
 
 // One batch of hinge_overlap_run_tiled: jobs[0..nj) (each whole, tiles of `tile` bases) against the resident block: k_overlap_vote_tile
 // over all their tiles, then k_overlap_tile_reduce per job; h_out = ovl_out_ints(max_partners) ints per job, h_top = one per job.
-static int overlap_batch_tiled(hinge_ctx* ctx, const OvlJob* jobs, size_t nj, const OvlParams& P, const OvlTileParams& TP, std::vector<OvlTileJob>& tj, std::vector<OvlRedJob>& rj,
+// S >= 1 (hinge_overlap_run_tiled_multi): k_overlap_vote_tile_multi and k_overlap_tile_reduce_multi with S rounds; a tile row and a
+// job's row are ovl_multi_out_ints(max_partners, S) ints.
+static int overlap_batch_tiled(hinge_ctx* ctx, const OvlJob* jobs, size_t nj, const OvlParams& P, const OvlTileParams& TP, int S, std::vector<OvlTileJob>& tj, std::vector<OvlRedJob>& rj,
                                std::vector<int>& h_out, std::vector<int>& h_top) {
     OverlapState* t = ctx->ovl_st;
     CnsState* s = ctx->cns;
@@ -66,7 +69,7 @@ static int overlap_batch_tiled(hinge_ctx* ctx, const OvlJob* jobs, size_t nj, co
         rj.push_back(OvlRedJob{(int)tj.size(), nt});
         for (int x = 0; x < nt; x++) tj.push_back(OvlTileJob{jobs[j].a, jobs[j].comp, jobs[j].alen, x});
     }
-    const size_t W = (size_t)ovl_out_ints(P.max_partners), nt = tj.size(), row_ints = nt * W, out_ints = nj * W;
+    const size_t W = (size_t)(S ? ovl_multi_out_ints(P.max_partners, S) : ovl_out_ints(P.max_partners)), nt = tj.size(), row_ints = nt * W, out_ints = nj * W;
     int rc;
     if ((rc = ensure(ctx, t->tjobs, sizeof(OvlTileJob) * nt))) return rc;
     if ((rc = ensure(ctx, t->tout, sizeof(int) * row_ints))) return rc;
@@ -79,16 +82,24 @@ static int overlap_batch_tiled(hinge_ctx* ctx, const OvlJob* jobs, size_t nj, co
     CK(hipMemsetAsync(t->out.p, 0xff, sizeof(int) * out_ints, ctx->stream));
     CK(hipMemsetAsync(t->top.p, 0xff, sizeof(int) * nj, ctx->stream));
     CnsSeqs SB{(const unsigned char*)s->bps[0].p, (const long long*)s->boff[0].p, (const int*)s->rlen[0].p};
-    {
+    if (S == 0) {
         ProfScope _ps(ctx, KID_OVERLAP_VOTE_TILE);
         hipLaunchKernelGGL(k_overlap_vote_tile, dim3((unsigned)nt), dim3(64), ovl_lds_bytes(P.list), ctx->stream, SB, (const OvlTileJob*)t->tjobs.p, (int)nt, P, TP,
                            (const unsigned*)t->codes.p, (const int*)t->gpos.p, (const long long*)t->off.p, (int*)t->tout.p);
+    } else {
+        ProfScope _ps(ctx, KID_OVERLAP_VOTE_TILE_MULTI);
+        hipLaunchKernelGGL(k_overlap_vote_tile_multi, dim3((unsigned)nt), dim3(64), ovl_multi_lds_bytes(P.list), ctx->stream, SB, (const OvlTileJob*)t->tjobs.p, (int)nt, P, TP, S,
+                           (const unsigned*)t->codes.p, (const int*)t->gpos.p, (const long long*)t->off.p, (int*)t->tout.p);
     }
     CK(hipGetLastError());
-    {
+    if (S == 0) {
         ProfScope _ps(ctx, KID_OVERLAP_TILE_REDUCE);
         hipLaunchKernelGGL(k_overlap_tile_reduce, dim3((unsigned)nj), dim3(64), 0, ctx->stream, (const int*)t->tout.p, (const OvlRedJob*)t->jobs.p, (int)nj, P.max_partners, TP.part_top,
                            (int*)t->out.p, (int*)t->top.p);
+    } else {
+        ProfScope _ps(ctx, KID_OVERLAP_TILE_REDUCE_MULTI);
+        hipLaunchKernelGGL(k_overlap_tile_reduce_multi, dim3((unsigned)nj), dim3(64), 0, ctx->stream, (const int*)t->tout.p, (const OvlRedJob*)t->jobs.p, (int)nj, P.max_partners,
+                           TP.part_top, S, P.window, (int*)t->out.p, (int*)t->top.p);
     }
     CK(hipGetLastError());
     h_out.resize(out_ints);
@@ -102,7 +113,8 @@ static int overlap_batch_tiled(hinge_ctx* ctx, const OvlJob* jobs, size_t nj, co
 }
 
 // hinge_overlap_run (S == 0: k_overlap_vote, one round) and hinge_overlap_run_multi (S = 1 .. 8 rounds of k_overlap_vote_multi).
-// T > 0 (with S == 0): hinge_overlap_run_tiled with tiles of T bases - other limits, the call's step for every read, batches by tile count.
+// T > 0: hinge_overlap_run_tiled (S == 0) and hinge_overlap_run_tiled_multi (S = 1 .. 8) with tiles of T bases - other limits, the call's
+// step for every read, batches by tile count.
 static int overlap_run_impl(hinge_ctx* ctx, const hinge_overlap_params* params, int S, int T, int32_t* status, int32_t* hits, int64_t* n_out) {
     if (!ctx || !ctx->cns || !n_out || (ctx->cns->n_seq[0] > 0 && !status))
         return fail(ctx, HINGE_E_ARG, "hinge_overlap_run / _run_multi: bad arguments (call hinge_consensus_set_db with the read DB for both DBs first)");
@@ -151,9 +163,11 @@ static int overlap_run_impl(hinge_ctx* ctx, const hinge_overlap_params* params, 
     for (int r = 0; r < 2 * n; r++) { status[r] = OVL_ST_NONE; if (hits) hits[r] = 0; }
     if (n == 0) return HINGE_OK;
     const size_t lds = ovl_lds_bytes(q.list);
-    if (T > 0 && lds > 48 * 1024) CK(hipFuncSetAttribute((const void*)k_overlap_vote_tile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (T > 0 && S == 0 && lds > 48 * 1024) CK(hipFuncSetAttribute((const void*)k_overlap_vote_tile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (T > 0 && S > 0 && ovl_multi_lds_bytes(q.list) > 48 * 1024)
+        CK(hipFuncSetAttribute((const void*)k_overlap_vote_tile_multi, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ovl_multi_lds_bytes(q.list)));
     if (S == 0 && T == 0 && lds > 48 * 1024) CK(hipFuncSetAttribute((const void*)k_overlap_vote, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (S > 0 && ovl_multi_lds_bytes(q.list) > 48 * 1024)
+    if (S > 0 && T == 0 && ovl_multi_lds_bytes(q.list) > 48 * 1024)
         CK(hipFuncSetAttribute((const void*)k_overlap_vote_multi, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ovl_multi_lds_bytes(q.list)));
     OvlParams P;
     P.k = q.k; P.window = q.window; P.max_occ = q.max_occ; P.list = q.list; P.max_partners = q.max_partners; P.min_hits = q.min_hits;
@@ -214,7 +228,7 @@ static int overlap_run_impl(hinge_ctx* ctx, const hinge_overlap_params* params, 
                     bytes += nt * per_tile + per_red; tiles += nt;
                 }
                 if (tiles > 0x7fffffffll / W) return fail(ctx, HINGE_E_CAPACITY, "hinge_overlap_run_tiled: one read's tile rows beyond 2^31 ints (a larger tile, or fewer max_partners)");
-                if ((rc = overlap_batch_tiled(ctx, jobs.data() + j0, (size_t)(j1 - j0), P, TP, tj, rj, h_out, h_top))) return rc;
+                if ((rc = overlap_batch_tiled(ctx, jobs.data() + j0, (size_t)(j1 - j0), P, TP, S, tj, rj, h_out, h_top))) return rc;
             } else if ((rc = overlap_batch(ctx, jobs.data() + j0, (size_t)(j1 - j0), P, S, h_out))) return rc;
             t->stats[0] += j1 - j0;
             t->stats[1]++;
@@ -285,6 +299,15 @@ int hinge_overlap_run_tiled(hinge_ctx* ctx, const hinge_overlap_params* params, 
     if (tile == 0) tile = (int32_t)seed_env("HINGE_OVERLAP_TILE", HINGE_OVERLAP_TILE_MAX);
     if (tile < 1) return fail(ctx, HINGE_E_ARG, "hinge_overlap_run_tiled: tile a power of two 64..8192, at most list * step (0 = HINGE_OVERLAP_TILE, else 8192)");
     return overlap_run_impl(ctx, params, 0, tile, status, hits, n_out);
+}
+
+int hinge_overlap_run_tiled_multi(hinge_ctx* ctx, const hinge_overlap_params* params, int32_t tile, int32_t max_stretches, int32_t* status, int32_t* hits, int64_t* n_out) {
+    if (tile == 0) tile = (int32_t)seed_env("HINGE_OVERLAP_TILE", HINGE_OVERLAP_TILE_MAX);
+    if (tile < 1) return fail(ctx, HINGE_E_ARG, "hinge_overlap_run_tiled_multi: tile a power of two 64..8192, at most list * step (0 = HINGE_OVERLAP_TILE, else 8192)");
+    if (max_stretches == 0) max_stretches = (int32_t)seed_env("HINGE_OVERLAP_TILE_STRETCHES", 1);
+    if (max_stretches < 1 || max_stretches > OVL_STRETCHES_MAX)
+        return fail(ctx, HINGE_E_ARG, "hinge_overlap_run_tiled_multi: max_stretches 1..8 (0 = HINGE_OVERLAP_TILE_STRETCHES, else 1)");
+    return overlap_run_impl(ctx, params, max_stretches, tile, status, hits, n_out);
 }
 
 int hinge_overlap_tile_stats(hinge_ctx* ctx, int64_t* out) {

@@ -1,5 +1,5 @@
 // overlap  ==  `hinge overlap READ_DB OUT.las [--k K] [--step S] [--window W] [--max-occ C] [--list L] [--max-partners N] [--min-hits H] [--block-bases B]
-//                              [--max-stretches S] [--tile T] [--min-len M] [--max-err E] [--tspace T] [--band W] [--band-max W]`
+//                              [--max-stretches S] [--tile T] [--tile-stretches S] [--min-len M] [--max-err E] [--tspace T] [--band W] [--band-max W]`
 // Not a program of the reference: it stands where the reference's run script calls DALIGNER (HPC.daligner + LAsort / LAmerge) on the
 // read DB against itself to get the read-vs-read .las that `hinge filter` opens.  The candidates - "reads a and b, strand, about this
 // diagonal" - are found by k-mer votes behind the C ABI (hinge_overlap_run, include/hinge_hip.h) and aligned by hinge_trace_local,
@@ -35,8 +35,13 @@
 //   alignment   a record of a read of more than one tile that begins or ends inside both reads - the box along a tile's diagonal cut
 //               it - runs through hinge_trace_local once more from its own end points with room for 1024 bases per side; the longer
 //               of the two stays
-//   Not together with --max-stretches above 1 (the usage, exit 1).  Not claimed: that the alignment of a placement of 2^20 or
-//   more bases succeeds - the option lifts the limit of the candidate search.
+//   Not together with --max-stretches above 1 (the usage, exit 1): --tile-stretches is the spelling for both.  Not claimed: that the
+//   alignment of a placement of 2^20 or more bases succeeds - the option lifts the limit of the candidate search.
+// --tile T --tile-stretches S (1..8; default HINGE_OVERLAP_TILE_STRETCHES, else 1; 1 is the --tile path above, call for call; needs a
+// tile; not with --max-stretches above 1): up to S records per (aread, bread, comp) from tiles
+//   candidates  hinge_overlap_run_tiled_multi: S rounds of pick and suppress in every tile, and again over the tiles' candidates
+//   behind them both blocks above, in this order: canonical frame and merge, alignment, the tiled path's second run, the duplicate
+//               rule, the mirrors tied by index, the output order of --max-stretches; both summary lines are printed
 // Not claimed: two stretches on one diagonal; a weaker stretch inside the band that a stronger one's alignment settles in (after a
 // TOUCHED widening both boxes may return the same optimum: the duplicate rule then leaves one); stretches of fewer than min-hits hits.
 #include "host_common.h"
@@ -47,11 +52,13 @@ using namespace hh;
 
 static void usage() {
     fprintf(stderr, "usage: overlap <read db> <out.las> [--k K] [--step S] [--window W] [--max-occ C] [--list L] [--max-partners N] [--min-hits H] [--block-bases B]\n"
-                    "               [--max-stretches S] [--tile T] [--min-len M] [--max-err E] [--tspace T] [--band W] [--band-max W]\n"
+                    "               [--max-stretches S] [--tile T] [--tile-stretches S] [--min-len M] [--max-err E] [--tspace T] [--band W] [--band-max W]\n"
                     "       read-vs-read overlaps of <read db> by k-mer votes and banded local alignment, as the .las `hinge filter` reads\n"
                     "       --max-stretches S: up to S (1..8) records per (aread, bread, strand), one per stretch; default HINGE_OVERLAP_MAX_STRETCHES, else 1\n"
                     "       --tile T: the candidates of every read from half-overlapping query tiles of T bases (a power of two 64..8192, at most list * step):\n"
-                    "                 reads of any length below 2^30 bases at --step; default HINGE_OVERLAP_TILE, else off; not with --max-stretches above 1\n");
+                    "                 reads of any length below 2^30 bases at --step; default HINGE_OVERLAP_TILE, else off; not with --max-stretches above 1\n"
+                    "       --tile-stretches S: with a tile, up to S (1..8) records per (aread, bread, strand) from the tiles; default HINGE_OVERLAP_TILE_STRETCHES, else 1;\n"
+                    "                 not with --max-stretches above 1\n");
 }
 
 // both reads whole along the record-frame diagonal (bbpos - abpos), clamped to both; the rule of overlap_project (overlap_kernels.h)
@@ -74,6 +81,7 @@ int main(int argc, char* argv[]) {
     double max_err = 0.30;
     int stretches = 0;                              // 0: not given
     int tile = 0;                                   // 0: not given
+    int tstretches = 0;                             // 0: not given
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto text = [&](const char* name) -> const char* {
@@ -98,6 +106,10 @@ int main(int argc, char* argv[]) {
             if (stretches > HINGE_OVERLAP_MAX_STRETCHES_LIMIT) { fprintf(stderr, "overlap: --max-stretches needs a number in 1..8\n"); usage(); return 1; }
         }
         else if (a == "--tile") tile = (int)val("--tile");
+        else if (a == "--tile-stretches") {
+            tstretches = (int)val("--tile-stretches");
+            if (tstretches > HINGE_OVERLAP_MAX_STRETCHES_LIMIT) { fprintf(stderr, "overlap: --tile-stretches needs a number in 1..8\n"); usage(); return 1; }
+        }
         else if (a == "--min-len") min_len = (int)val("--min-len");
         else if (a == "--tspace") tspace = (int)val("--tspace");
         else if (a == "--band") band = (int)val("--band");
@@ -117,14 +129,24 @@ int main(int argc, char* argv[]) {
         stretches = (g && *g) ? atoi(g) : 1;
         if (stretches < 1 || stretches > HINGE_OVERLAP_MAX_STRETCHES_LIMIT) { fprintf(stderr, "overlap: HINGE_OVERLAP_MAX_STRETCHES needs a number in 1..8\n"); usage(); return 1; }
     }
-    const bool multi = stretches > 1;
+    const bool tstretches_given = tstretches != 0;
+    if (tstretches == 0) {
+        const char* g = getenv("HINGE_OVERLAP_TILE_STRETCHES");
+        tstretches = (g && *g) ? atoi(g) : 1;
+        if (tstretches < 1 || tstretches > HINGE_OVERLAP_MAX_STRETCHES_LIMIT) { fprintf(stderr, "overlap: HINGE_OVERLAP_TILE_STRETCHES needs a number in 1..8\n"); usage(); return 1; }
+    }
+    if ((tstretches_given || tstretches > 1) && stretches > 1) { fprintf(stderr, "overlap: --tile-stretches and --max-stretches above 1 do not go together\n"); usage(); return 1; }
+    const bool tmulti = tstretches > 1;             // the candidates from hinge_overlap_run_tiled_multi; behind them --max-stretches' blocks and --tile's
+    const bool multi = stretches > 1 || tmulti;
+    if (tmulti) stretches = tstretches;
     if (tile == 0) {
         const char* g = getenv("HINGE_OVERLAP_TILE");
         if (g && *g) tile = atoi(g);
         if (g && *g && tile < 1) { fprintf(stderr, "overlap: HINGE_OVERLAP_TILE needs a power of two in 64..8192\n"); usage(); return 1; }
     }
     if (tile != 0 && (tile < 64 || tile > HINGE_OVERLAP_TILE_MAX || (tile & (tile - 1)))) { fprintf(stderr, "overlap: --tile needs a power of two in 64..8192\n"); usage(); return 1; }
-    if (tile != 0 && multi) { fprintf(stderr, "overlap: --tile and --max-stretches above 1 do not go together\n"); usage(); return 1; }
+    if (tile != 0 && multi && !tmulti) { fprintf(stderr, "overlap: --tile and --max-stretches above 1 do not go together (--tile-stretches)\n"); usage(); return 1; }
+    if (tile == 0 && (tstretches_given || tmulti)) { fprintf(stderr, "overlap: --tile-stretches needs a tile (--tile or HINGE_OVERLAP_TILE)\n"); usage(); return 1; }
     PhaseTimer tm("overlap");
     CtxInit gpu;
     gpu.start();
@@ -145,7 +167,8 @@ int main(int argc, char* argv[]) {
     // ---- the candidates, made symmetric ------------------------------------------------------------------------------------------
     std::vector<int32_t> jstatus((size_t)std::max(2 * n_reads, 2));
     int64_t n_cand = 0;
-    if ((multi ? hinge_overlap_run_multi(ctx, &prm, stretches, jstatus.data(), nullptr, &n_cand)
+    if ((tmulti ? hinge_overlap_run_tiled_multi(ctx, &prm, tile, stretches, jstatus.data(), nullptr, &n_cand)
+         : multi ? hinge_overlap_run_multi(ctx, &prm, stretches, jstatus.data(), nullptr, &n_cand)
          : tile ? hinge_overlap_run_tiled(ctx, &prm, tile, jstatus.data(), nullptr, &n_cand)
                 : hinge_overlap_run(ctx, &prm, jstatus.data(), nullptr, &n_cand)) != HINGE_OK) die("votes");
     std::vector<hinge_cns_alignment> cand((size_t)std::max<int64_t>(n_cand, 1));
@@ -422,7 +445,7 @@ int main(int argc, char* argv[]) {
     if (multi) {
         std::string rounds;
         for (int r = 0; r < stretches; r++) rounds += (r ? " + " : "") + std::to_string((long long)per_round[(size_t)r]);
-        printf("overlap: --max-stretches %d: %s candidates per round, %lld merged into clusters, %lld clusters, %lld duplicates dropped\n", stretches, rounds.c_str(), (long long)merged,
+        printf("overlap: %s %d: %s candidates per round, %lld merged into clusters, %lld clusters, %lld duplicates dropped\n", tmulti ? "--tile-stretches" : "--max-stretches", stretches, rounds.c_str(), (long long)merged,
                (long long)n, (long long)duplicates);
     }
     if (tile)

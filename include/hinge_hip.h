@@ -614,7 +614,23 @@ int hinge_seed_last_stats(hinge_ctx* ctx, int64_t* out);
  *   HINGE_OVERLAP_SCRATCH_MB; a job's tiles stay in one batch.  hinge_overlap_fetch, hinge_overlap_fetch_round (all 0) and
  *   hinge_overlap_last_stats serve it as they serve hinge_overlap_run.  hinge_overlap_tile_stats: out[0] tiles launched, [1] jobs
  *   of more than one tile, [2] the largest tile's kept hits, [3] reduce launches (all 0 after the other two calls).
- *   Not claimed for it: tiles together with max_stretches; that hinge_trace_local aligns a placement of 2^20 or more bases.
+ *   Not claimed for it: more than one candidate per (a, b, strand) (hinge_overlap_run_tiled_multi has those); that
+ *   hinge_trace_local aligns a placement of 2^20 or more bases.
+ * hinge_overlap_run_tiled_multi: hinge_overlap_run_tiled with up to max_stretches candidates per (a, b, strand).
+ *   tile as there (0 = HINGE_OVERLAP_TILE, else 8192); max_stretches 1..8, 0 = HINGE_OVERLAP_TILE_STRETCHES, else 1; anything
+ *   else is HINGE_E_ARG.  Every tile runs hinge_overlap_run_multi's rounds on its own hit list (k_overlap_vote_tile_multi,
+ *   overlap_tile_multi_kernels.h); a tile row has max_stretches sections, each in ascending b.  Per (read, strand, block)
+ *   k_overlap_tile_reduce_multi runs the rounds again over all sections of all tile rows: round r's pick of b is its LIVE tile
+ *   candidate of the largest cnt, of equal ones the lowest tile's, within a tile the lowest section's; afterwards every tile
+ *   candidate of b with |d - d_pick| < window is dead (one exactly `window` away stays live); a b without a live candidate has
+ *   none later.  Round r keeps its first max_partners partners in ascending b (TRUNCATED beyond, or if a tile row was); OVERFLOW
+ *   if a tile dropped hits; hits = the sum of the tiles' kept hits.  Every value of max_stretches, 1 included, runs these two
+ *   kernels: at 1 every output equals hinge_overlap_run_tiled's, and on reads of one tile every output equals
+ *   hinge_overlap_run_multi's at the same max_stretches.  Limits, blocks, errors and batches (a tile row is max_stretches times
+ *   as wide) are hinge_overlap_run_tiled's; hinge_overlap_fetch, hinge_overlap_fetch_round, hinge_overlap_last_stats and
+ *   hinge_overlap_tile_stats serve it; the candidates are sorted by (aread, bread, comp, round).
+ *   Not claimed for it: two stretches less than `window` apart; that a drifting overlap takes one slot only (tiles whose
+ *   diagonals spread over `window` or more give a second candidate).
  * Not claimed: chaining; a second stretch of the same pair by hinge_overlap_run (hinge_overlap_run_multi: not two stretches on
  *   one diagonal - less than `window` apart -, not a weaker stretch inside the band a stronger one's alignment settles in, not a
  *   stretch of fewer than min_hits hits); k-mers of more than max_occ copies per block; reads of 2^20 or more bases; more than
@@ -632,6 +648,7 @@ int hinge_overlap_run_multi(hinge_ctx* ctx, const hinge_overlap_params* params, 
 int hinge_overlap_fetch_round(hinge_ctx* ctx, int64_t cap, int32_t* round);
 #define HINGE_OVERLAP_TILE_MAX 8192
 int hinge_overlap_run_tiled(hinge_ctx* ctx, const hinge_overlap_params* params, int32_t tile, int32_t* status, int32_t* hits, int64_t* n_out);
+int hinge_overlap_run_tiled_multi(hinge_ctx* ctx, const hinge_overlap_params* params, int32_t tile, int32_t max_stretches, int32_t* status, int32_t* hits, int64_t* n_out);
 int hinge_overlap_tile_stats(hinge_ctx* ctx, int64_t* out);
 /* Of the last hinge_overlap_run / hinge_overlap_run_multi: out[0] jobs (read, strand, block), [1] batches, [2] blocks, [3] index entries (all blocks), [4] codes
  * dropped by max_occ, [5] OVERFLOW jobs, [6] TRUNCATED jobs, [7] microseconds of the indexes (whichever path built them:

@@ -15,9 +15,13 @@ hinge_overlap_run_multi at 1, 2 and 4 stretches, each kernel's time by HIP event
 k_overlap_tile_reduce_ms in place of k_overlap_vote_ms, tile_stats) and `hinge overlap --tile T` with --cli; with --ab N: N
 interleaved repetitions of hinge_overlap_run and hinge_overlap_run_tiled, each kernel's time by HIP events (tile_ab_ms: every run, the
 medians and the ratio of the tiled kernels' time to k_overlap_vote's).
+--tile T --tile-stretches S: everything through hinge_overlap_run_tiled_multi with S rounds (k_overlap_vote_tile_multi_ms and
+k_overlap_tile_reduce_multi_ms, candidates_per_round) and `hinge overlap --tile T --tile-stretches S` with --cli; with --ab N: N
+interleaved repetitions of hinge_overlap_run_tiled and hinge_overlap_run_tiled_multi at 1, 2 and 4 rounds, every kernel's time by
+HIP events (tile_multi_ab_ms: every run and the medians of the vote kernel, the reduce and their sum).
 There is no reference program for this step here (DALIGNER is not part of the reference tree): no speed-up factor is claimed.
 
-    python tools/overlap_bench.py [--config cns_bench] [--steps 2] [--align 200000] [--cli] [--keep DIR] [--max-stretches S] [--ab N] [--tile T]
+    python tools/overlap_bench.py [--config cns_bench] [--steps 2] [--align 200000] [--cli] [--keep DIR] [--max-stretches S] [--ab N] [--tile T] [--tile-stretches S]
 """
 import argparse
 import json
@@ -66,6 +70,7 @@ def main():
     ap.add_argument("--max-stretches", type=int, default=0)
     ap.add_argument("--ab", type=int, default=0)
     ap.add_argument("--tile", type=int, default=0)
+    ap.add_argument("--tile-stretches", type=int, default=0)
     args = ap.parse_args()
     import numpy as np
     import consensus_common as cc
@@ -86,9 +91,12 @@ def main():
     t = time.time()
     S = args.max_stretches
     T = args.tile
+    TS = args.tile_stretches
     assert not (S and T), "--tile and --max-stretches do not go together"
-    kernel = "k_overlap_vote_multi" if S else "k_overlap_vote_tile" if T else "k_overlap_vote"
-    res = ctx.overlap_run(max_stretches=S, tile=T)                                               # warm-up (allocations)
+    assert T or not TS, "--tile-stretches needs --tile"
+    kernel = "k_overlap_vote_multi" if S else "k_overlap_vote_tile_multi" if TS else "k_overlap_vote_tile" if T else "k_overlap_vote"
+    reduce_kernel = "k_overlap_tile_reduce_multi" if TS else "k_overlap_tile_reduce"
+    res = ctx.overlap_run(max_stretches=S, tile=T, tile_stretches=TS)                            # warm-up (allocations)
     pl, count, diag, rep, status, hits = res[:6]
     out["first_call_s"] = round(time.time() - t, 3)
     out["stats"] = ctx.overlap_stats()
@@ -97,7 +105,7 @@ def main():
     t = time.time()
     index_us = []
     for _ in range(args.steps):
-        res = ctx.overlap_run(max_stretches=S, tile=T)
+        res = ctx.overlap_run(max_stretches=S, tile=T, tile_stretches=TS)
         index_us.append(ctx.overlap_stats()["index_us"])
     ist = ctx.index_last_stats()
     out["index_stats"] = ist
@@ -112,10 +120,10 @@ def main():
     if T:
         out["tile"] = T
         out["tile_stats"] = ctx.overlap_tile_stats()
-        put("k_overlap_tile_reduce_ms", round(prof["k_overlap_tile_reduce"][0] / max(args.steps, 1), 3), "gpu")
-    if S:
-        out["max_stretches"] = S
-        put("candidates_per_round", [int((res[6] == r).sum()) for r in range(S)], "gpu")
+        put(reduce_kernel + "_ms", round(prof[reduce_kernel][0] / max(args.steps, 1), 3), "gpu")
+    if S or TS:
+        out["tile_stretches" if TS else "max_stretches"] = S or TS
+        put("candidates_per_round", [int((res[6] == r).sum()) for r in range(S or TS)], "gpu")
     put("run_call_ms", round(call_ms, 3), "host")
     put("candidates", int(len(pl)), "gpu")
     put("candidates_per_s", round(len(pl) / (kernel_ms * 1e-3)) if kernel_ms else None, "gpu")
@@ -135,7 +143,24 @@ def main():
     prof = ctx.profile_report()
     put("trace_local_ms", {"kernels_ms": round(sum(v[0] for k, v in prof.items() if k.startswith("k_trace")), 3), "call_s": round(wall, 3), "candidates": int(len(part)),
                            "of": int(len(sym)), "records": int((st[:, 0] == 0).sum())}, "gpu")
-    if args.ab and T:
+    if args.ab and TS:
+        names = ["tiled"] + ["tiled_multi S=%d" % x for x in (1, 2, 4)]
+        runs = {n: {"vote": [], "reduce": [], "sum": []} for n in names}
+        per_round = {}
+        for _ in range(args.ab):
+            for name in names:
+                s_ab = int(name.split("=")[1]) if "=" in name else 0
+                ctx.profile_enable(4096)
+                res = ctx.overlap_run(tile=T, tile_stretches=s_ab)
+                rp = ctx.profile_report()
+                v, r = (rp["k_overlap_vote_tile_multi"][0], rp["k_overlap_tile_reduce_multi"][0]) if s_ab else (rp["k_overlap_vote_tile"][0], rp["k_overlap_tile_reduce"][0])
+                runs[name]["vote"].append(round(v, 3)); runs[name]["reduce"].append(round(r, 3)); runs[name]["sum"].append(round(v + r, 3))
+                if s_ab:
+                    per_round[name] = [int((res[6] == x).sum()) for x in range(s_ab)]
+            print("overlap_bench: a/b repetition done", file=sys.stderr, flush=True)
+        put("tile_multi_ab_ms", {"runs": runs, "median": {n: {k: float(np.median(v)) for k, v in runs[n].items()} for n in names}}, "gpu")
+        put("tile_multi_ab_candidates_per_round", per_round, "gpu")
+    elif args.ab and T:
         runs = {"k_overlap_vote": [], "k_overlap_vote_tile": [], "k_overlap_tile_reduce": []}
         for _ in range(args.ab):
             ctx.profile_enable(4096)
@@ -166,7 +191,7 @@ def main():
     if args.cli:
         print("overlap_bench: the executable", file=sys.stderr, flush=True)
         t = time.time()
-        r = subprocess.run([os.path.join(ROOT, "hinge_amd", "bin", "hinge"), "overlap", "reads", "reads.las"] + (["--max-stretches", str(S)] if S else []) + (["--tile", str(T)] if T else []), cwd=wd, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+        r = subprocess.run([os.path.join(ROOT, "hinge_amd", "bin", "hinge"), "overlap", "reads", "reads.las"] + (["--max-stretches", str(S)] if S else []) + (["--tile", str(T)] if T else []) + (["--tile-stretches", str(TS)] if TS else []), cwd=wd, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
         assert r.returncode == 0, r.stderr.decode()[-2000:]
         put("records_written", {"summary": r.stdout.decode().strip(), "stderr": r.stderr.decode().strip().splitlines()[-1:], "wall_s": round(time.time() - t, 3)}, "gpu")
     else:
